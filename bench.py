@@ -15,6 +15,13 @@ fixed, so scaling is "strong"; value = queries/s over the whole corpus.
 CPU restatement (oracle/, test infrastructure; --graph-build gpu builds it
 with wv_index_build_graph instead) on SIFT-shaped data; reports QPS and
 recall@10 next to the restatement's on the same graph.
+
+A plain run sets up, warms up, times --steps steps of the chosen workload and
+prints its line.  --full adds everything else the line used to carry: the CPU
+baselines and parity samples, the wide-k / SearchByVectorDistance lines, the
+configs[0] / [2] / [3] / [4] lines beside the exact value, the caller-
+concurrency and open-loop legs, and at N > 1 the corpus-sharded and in-process
+group legs.  --dump-outputs DIR saves what the last timed step returned.
 """
 from __future__ import annotations
 
@@ -158,6 +165,27 @@ def parity_stats(gi, gd, oi, od):
                     break
         tie_ok += ok
     return id_eq, d_eq, tie_ok / max(len(gi), 1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, one
+    DIR/<name>.npy each -- ids and counts as float64 (ids are exact below 2^53;
+    an empty slot's id 2^64-1 rounds to 2^64), distances as float32.  Past 64 MB
+    in all, a fixed seeded sample of the query rows (saved as rows.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {k: np.asarray(a).astype(np.float64 if np.asarray(a).dtype.kind in "iu" else np.float32)
+            for k, a in arrays.items()}
+    nq = len(next(iter(conv.values())))
+    per_row = sum(a.nbytes // max(nq, 1) for a in conv.values()) + 8
+    if nq * per_row > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_LIMIT_BYTES // per_row, replace=False))
+        conv = {k: a[rows] for k, a in conv.items()}
+        conv["rows"] = rows.astype(np.float64)
+    for k, a in conv.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def dist_env():
@@ -488,6 +516,9 @@ def run_exact(args, ctx, W):
     fin_ids, fin_d = (m_ids, m_d) if (split == "corpus" and ws > 1) else (out_ids, out_d)
     final_ids = fin_ids.cpu().numpy().view(np.uint64)
     final_d = fin_d.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        fin_n = m_n if (split == "corpus" and ws > 1) else out_n
+        dump_outputs(args.dump_outputs, ids=final_ids, dists=final_d, counts=fin_n.cpu().numpy())
     units = NQ * (ws if split == "query" else 1)
     res = {
         "value": round(units * args.steps / elapsed, 1),
@@ -843,6 +874,8 @@ def run_hnsw(args, ctx, W, with_cpu):
     hi_d = fin[1].cpu().numpy().copy()
     shard_ids = out_ids.cpu().numpy().view(np.uint64).copy()   # this rank's own shard answer
     shard_d = out_d.cpu().numpy().copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ids=hi_ids, dists=hi_d, counts=(m_n if corpus else out_n).cpu().numpy())
     # exact truths on the same queries (the exact path: ids bit-identical to
     # flatSearch; per shard + the same merge in the corpus layout), timed
     # once: SIFT-shaped data is integer-valued, so equal distances at the k
@@ -1316,6 +1349,13 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=["exact", "hnsw"], default="exact")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed line: the CPU baselines and parity samples, the wide-k lines, the "
+                         "configs[0]/[2]/[3]/[4] lines, the concurrency and open-loop legs, the N>1 corpus-sharded and "
+                         "group legs (each has its own --no-... switch); without it only the headline steps run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed step returned as DIR/ids.npy, dists.npy, counts.npy "
+                         "(float64 / float32)")
     ap.add_argument("--split", choices=["query", "corpus"], default="",
                     help="N>1: query = every GPU holds the corpus and answers its own batch (default, weak scaling); "
                          "corpus = id-range shards + RCCL all-gather + device merge (strong scaling)")
@@ -1392,6 +1432,11 @@ def main():
     ap.add_argument("--group-leg", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--group-devices", default="0", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full and not args.group_leg:
+        # a plain run does what its headline needs and nothing else
+        args.no_cpu_baseline = args.no_wide_line = args.no_hnsw_line = args.no_c3_line = True
+        args.no_c4_line = args.no_c5_line = args.no_corpus_leg = args.no_group_leg = True
+        args.seq_build, args.concurrency, args.open_loop = False, "", ""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from build_hash import host_cores_info
     args.host_cores = host_cores_info()
@@ -1477,6 +1522,7 @@ def main():
             st["ix"].close()
             a2 = argparse.Namespace(**vars(args))
             a2.split = "corpus"
+            a2.dump_outputs = ""
             c, cst = run_exact(a2, ctx, W)
             result["corpus_sharded"] = {
                 "value": c["value"], "unit": "queries/s", "ms_per_step": c["ms_per_step"], "scaling": "strong",
@@ -1493,7 +1539,7 @@ def main():
             a1 = argparse.Namespace(**vars(args))
             a1.seq_build = (args.seq_build or (not args.no_seq_build and args.rows == 1_000_000)) and ws == 1
             a1.filtered_fracs = [] if args.no_filtered_hnsw else [0.1, 0.5, 0.01]
-            a1.dump_ids = ""   # (--dump-ids holds the exact line's answers)
+            a1.dump_ids = a1.dump_outputs = ""   # (--dump-ids / --dump-outputs hold the exact line's answers)
             phase("configs[0] hnsw line")
             h = run_hnsw(a1, ctx, W, with_cpu)
             h.pop("metric", None)
@@ -1504,6 +1550,7 @@ def main():
             a3.rows, a3.dim, a3.metric, a3.hnsw_data = 1_200_000, 100, "cosine-dot", "glove"
             a3.ef, a3.ef_sweep, a3.concurrency, a3.split = 64, [32, 64, 128, 256], [], "corpus"
             a3.cpu_seconds, a3.cpu_seconds_t1, a3.graph_build, a3.dump_ids = 4.0, 2.0, "gpu", ""
+            a3.dump_outputs = ""
             # north_star's 0.5-pt recall check against the insert-by-insert
             # graph at this line's ef and 128 (~50 s of CPU at 1.2M rows)
             a3.seq_build = not args.no_seq_build and ws == 1
@@ -1537,6 +1584,7 @@ def main():
             a5.ef, a5.ef_sweep, a5.concurrency, a5.split = 128, [64], [], "corpus"
             a5.graph_build, a5.dump_ids, a5.seq_build = "gpu", "", False
             a5.device_data = True
+            a5.dump_outputs = ""
             a5.counts_sample, a5.exact_counts_sample = 0, 1000
             try:
                 phase("configs[4] hnsw over the 100M corpus")

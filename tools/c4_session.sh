@@ -5,7 +5,7 @@
 # Outputs under gpurun_out/c4/.
 export TMPDIR=/tmp
 O=gpurun_out/c4; mkdir -p $O
-A="--rows 1250000 --dim 768 --metric dot --nq 1000 --data gauss --no-hnsw-line --no-c3-line --no-wide-line --steps 5 --warmup 2"
+A="--full --rows 1250000 --dim 768 --metric dot --nq 1000 --data gauss --no-hnsw-line --no-c3-line --no-wide-line --steps 5 --warmup 2"
 for p in ${PS:-0 0.5 0.1 0.01}; do
   timeout -k 10 300 python3 -u bench.py $A --allow-frac $p --cpu-seconds 6 --cpu-seconds-t1 3 > $O/bench_$p.jsonl 2> $O/bench_$p.err || { echo "bench $p failed"; exit 1; }
   tail -c 400 $O/bench_$p.jsonl

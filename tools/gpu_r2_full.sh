@@ -5,6 +5,8 @@
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-r2}
+# (the default bench line with all its legs is bench.py --full)
+BENCH_ARGS="--full ${BENCH_ARGS}"; PROF_ARGS="--full ${PROF_ARGS}"
 stop() { case $1 in 124|134|137|139) echo "stopping after rc=$1"; exit $1;; esac; }
 KARGS=()
 [ -n "$TEST_K" ] && KARGS=(-k "$TEST_K")

@@ -11,9 +11,9 @@ tail -3 $O/gputests.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 fi
-timeout -k 10 600 python -u bench.py > $O/bench.jsonl 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.jsonl 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 tail -c 300 $O/bench.jsonl
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u bench.py --no-cpu-baseline > $O/prof.log 2>&1 || { tail -5 $O/prof.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 -u bench.py --full --no-cpu-baseline > $O/prof.log 2>&1 || { tail -5 $O/prof.log; exit 1; }
 # (the per-dispatch trace is tens of MiB: keep the stats, gzip the trace)
 gzip -f $O/prof/run_kernel_trace.csv; ls -la $O/prof
 echo done

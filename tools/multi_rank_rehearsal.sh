@@ -3,7 +3,7 @@
 # and N=4 ranks sharing cuda:0 with the gloo backend; the merged ids/dists of
 # every N must equal N=1's bit for bit (exact mode).
 mkdir -p gpurun_out
-A="--steps 2 --warmup 1 --no-cpu-baseline --rows ${RN:-200000} --nq 2000"
+A="--full --steps 2 --warmup 1 --no-cpu-baseline --rows ${RN:-200000} --nq 2000"
 timeout -k 10 300 python -u bench.py $A --dump-ids /tmp/ids1.npz > gpurun_out/rank1.log 2>&1 || exit $?
 tail -1 gpurun_out/rank1.log | cut -c1-300
 for n in 2 4; do

@@ -18,7 +18,7 @@ LINE=${LINE:-head}
 G=gpurun_out/pmc_bench; mkdir -p $G/$LINE
 O=/tmp/pmc_bench/$LINE; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
-OFF="--no-cpu-baseline --no-corpus-leg --no-group-leg --no-wide-line --steps 5 --warmup 2"
+OFF="--full --no-cpu-baseline --no-corpus-leg --no-group-leg --no-wide-line --steps 5 --warmup 2"
 case $LINE in
   head) ARGS="$OFF --no-hnsw-line --no-c3-line --no-c4-line --no-c5-line"
         KNAME=wv_bf_h16_kernel; KSUB="wv_bf_h16_kernel<8, true, false, true>"; SHAPE="1000000 10000 128 uniform"
@@ -32,7 +32,7 @@ case $LINE in
         KNAME=wv_bf_h16w_kernel; KSUB="wv_bf_h16w_kernel<false, 128>"; SHAPE="10000000 1000 768 gauss_allow$FR"
         OUTJ=pmc_wv_bf_h16w_kernel_c4_$F.json; T=300;;
   c3t1) # (the tombstoned leg needs the restatement's counts: CPU baseline on, short)
-        ARGS="--no-corpus-leg --no-group-leg --no-wide-line --steps 5 --warmup 2 --cpu-seconds 2 --cpu-seconds-t1 1"
+        ARGS="--full --no-corpus-leg --no-group-leg --no-wide-line --steps 5 --warmup 2 --cpu-seconds 2 --cpu-seconds-t1 1"
         ARGS="$ARGS --no-hnsw-line --no-c4-line --no-c5-line --no-seq-build"
         KNAME=wv_hnsw_side_kernel; KSUB="wv_hnsw_side_kernel<2, 1, 3, 3, false>"; SHAPE="1200000 10000 100 glove"
         AF="tomb:0.01"; OUTJ=pmc_wv_hnsw_side_kernel_c3t1.json; T=300;;

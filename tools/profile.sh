@@ -2,7 +2,7 @@
 # rocprofv3 passes over bench.py: kernel trace + stats, then PMC counters in
 # separate passes (never combined with tracing).  Outputs: gpurun_out/prof_<tag>/.
 TAG=${1:-r01}
-ARGS=${BENCH_ARGS:-"--no-cpu-baseline --steps 3 --warmup 1"}
+ARGS=${BENCH_ARGS:-"--full --no-cpu-baseline --steps 3 --warmup 1"}
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT

@@ -100,17 +100,67 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     // the image words this wave moves per tile (its share, and the s|x|^2
     // word on wave 0): a lane offset per share, computed once
     const uint32_t voff = (uint32_t)(wave * 1024 + lane * 16);
-    auto fill = [&](uint64_t t, int st) {
-        const uint64_t tile = p.tile_base + t * (uint64_t)p.tile_stride;
-        const uint32_t dst = lds0 + (uint32_t)(st * St::U4 * 16) + (uint32_t)(wave * 1024);
-        const uint4* src = uniform_ptr(X + tile * St::IMG_U4);
-#pragma unroll
-        for (int i = 0; i < St::IMG_U4 / 64; i += WAVES)
-            if (wave + i < St::IMG_U4 / 64) glds16s(src, voff + (uint32_t)(i * 1024), dst + (uint32_t)(i * 1024));
-        if (wave == 0 && L2) glds4(p.xns + tile * H_BN + lane, dst + St::IMG_U4 * 16);
-    };
 
-    // the tiles of stage-group g (TPS consecutive tiles) into LDS stage g % 3
+    // The tile stream as running scalar state (the tile index advances by
+    // one, with at most one wrap per segment): nothing in the tile loop
+    // multiplies, and nothing compares 64-bit tile indices -- gfx950 has no
+    // scalar ordered 64-bit compare, so each such `>=` was a VALU compare
+    // whose VCC a scalar branch then waited for.  Tile counts fit 32 bits
+    // (tile_okw reads the words by a 32-bit index).
+    //
+    // A tile's LDS-DMA ops, per wave: image KiB `wave` and, past 8 KiB,
+    // `wave + 8`, then (L2, wave 0) the tile's s|x|^2 word -- entry i of OPT.
+    // The fill state is the next tile to fetch: its corpus tile index (+ the
+    // stride per tile, - the scanned range once at the rotation's wrap), its
+    // LDS address, and the tiles left.  An op's source is X or xns + that
+    // index x a tile's bytes -- a shift at D = 128.  (Running 64-bit
+    // pointers instead, with their steps and spans, held ten more SGPRs over
+    // the loop: + 8 spill lanes in the D = 128 instantiations.)
+    constexpr int NIMG = St::IMG_U4 / 64 > WAVES ? 2 : 1;
+    static_assert(St::IMG_U4 / 64 <= 2 * WAVES, "a wave moves at most two image KiB per tile");
+    constexpr int OPT = NIMG + (L2 ? 1 : 0);
+    // corpus tile index of a scanned tile: 32-bit, + ct_step per tile, - ct_span past ct_end
+    const uint32_t ct_step = (uint32_t)p.tile_stride, ct_span = (uint32_t)(p.ntiles * (uint64_t)p.tile_stride);
+    const uint32_t ct_end = (uint32_t)p.tile_base + ct_span;
+    const uint32_t dst_first = lds0 + (uint32_t)(wave * 1024), dst_end = dst_first + (uint32_t)(NSTG * TPS * St::U4 * 16);
+    uint32_t f_ct = 0, f_dst = dst_first;
+    int f_left = 0;   // tiles of the segment not handed to a burst yet
+    int f_now = 0;    // tiles of the burst being issued
+    auto fill_op = [&](int i) {
+        if (i < NIMG) {
+            if (wave + WAVES * i < St::IMG_U4 / 64)
+                glds16s(uniform_ptr(X + (uint64_t)f_ct * St::IMG_U4), voff + (uint32_t)(i * WAVES * 1024),
+                        f_dst + (uint32_t)(i * WAVES * 1024));
+        } else if (wave == 0) {
+            glds4s(uniform_ptr(p.xns + (uint64_t)f_ct * H_BN), (uint32_t)(lane * 4), f_dst + St::IMG_U4 * 16);
+        }
+        if (i == OPT - 1) {   // the tile's last entry: on to the next tile
+            f_ct += ct_step;
+            if (f_ct >= ct_end) f_ct -= ct_span;
+            f_dst += (uint32_t)(St::U4 * 16);
+            if (f_dst == dst_end) f_dst = dst_first;
+            --f_now;
+        }
+    };
+    // Burst issue inside the MFMA stream: a group's OPT * TPS entries at
+    // fixed places of the two halves (A, E) that follow the group barrier,
+    // OPK per k-step from the first k-step on -- one wherever the halves
+    // have the k-steps for it (NS >= 3).  Every wave then issues between its
+    // own MFMAs instead of all eight at once behind the barrier.
+    constexpr int OPK = (OPT * TPS + 2 * NS - 1) / (2 * NS);
+    static_assert(OPT * TPS <= 2 * NS * OPK, "a burst fits the two halves after its barrier");
+    constexpr bool DMA_IN_E = OPT * TPS > NS * OPK;   // (entries left over for phase E)
+    auto dma_steps = [&](int half) {
+        return [&, half](int k) {
+#pragma unroll
+            for (int o = 0; o < OPK; ++o) {
+                const int e = (half * NS + k) * OPK + o;
+                if (e < OPT * TPS && f_now > 0) fill_op(e % OPT);
+            }
+        };
+    };
+    auto no_dma = [](int) {};
+
     // (locality bit 2: a query block's tiles rotated by its first block's
     // offset, so that every query block's slot boundaries fall on the same
     // tiles -- the blocks scanning a tile together, in one XCD's L2 with the
@@ -120,18 +170,10 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         const uint64_t v = t + shift;
         return v >= p.ntiles ? v - p.ntiles : v;
     };
-    auto fill_group = [&](uint64_t t_begin, int g, int ntile) {
-        const int st = g % NSTG;
-        int n = 0;
-#pragma unroll
-        for (int j = 0; j < TPS; ++j) {
-            const int t = g * TPS + j;
-            if (t < ntile) { fill(phys(t_begin + t), st * TPS + j); ++n; }
-        }
-        return n * n_ops;   // this wave's DMA ops for the group
-    };
     // (in the tile loop: the slot of tile t advances by one, wrapping at the ring)
     auto next_slot = [](int sl) { return sl + 1 == NSTG * TPS ? 0 : sl + 1; };
+    const uint32_t clean32 = (uint32_t)(p.clean_tiles < 0xFFFFFFFFull ? p.clean_tiles : 0xFFFFFFFFull);
+    const uint32_t full32 = (uint32_t)(p.N / H_BN < 0xFFFFFFFFull ? p.N / H_BN : 0xFFFFFFFFull);
 
     for (uint64_t u = u_first; u < u_last;) {
         const int qb = (int)(u / p.ntiles);
@@ -220,7 +262,9 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         // harmless re-read of img).  The order is pinned with scheduling
         // fences: the compiler's own schedule hoisted every read to the
         // front and drained them all before the first MFMA.
-        auto mfma_half = [&](const uint4* img, int rb, floatx16& accA, floatx16& accB, auto&& between,
+        // `dma(k)`: this k-step's share of a fill burst (dma_steps above), a
+        // DMA issue between two MFMAs.
+        auto mfma_half = [&](const uint4* img, int rb, floatx16& accA, floatx16& accB, auto&& between, auto&& dma,
                              const uint4* nimg, int nrb) {
             floatx16 xc;
             if (L2) xc = xcn;
@@ -257,6 +301,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 // more per tile)
                 if (k == 0) asm volatile("" ::"v"(xc));
 #endif
+                dma(k);
                 between(k);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -289,16 +334,18 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         // eligibility of a tile's 64 rows for this lane's two columns (bits of
         // rows 4 khalf + ..., low word: rows 0-31, high word: rows 32-63)
         // (the lane-dependent shifts happen only when a tile needs the mask)
-        auto tile_ok = [&](uint64_t t, uint64_t& okw) -> bool {
-            const uint64_t ct = p.tile_base + t * (uint64_t)p.tile_stride;
-            if (ct < p.clean_tiles) {   // (the host's clean prefix: no word to read)
+        // (ct: the corpus tile's index, the loop's running 32-bit state)
+        auto tile_ok = [&](uint32_t ct, uint64_t& okw) -> bool {
+            if (ct < clean32) {   // (the host's clean prefix: no word to read)
                 okw = ~0ull;
                 return false;
             }
-            okw = tile_okw(p, ct, has_allow);
+            okw = tile_okw32(p, ct, full32, has_allow);
             return okw != ~0ull;
         };
-        auto lane_ok = [&](uint64_t okw, int jq) -> uint64_t { return (jq < p.nq ? okw : 0ull) >> (4 * khalf); };
+        // (one 32-row half's word: the bits mask_half reads, (r & 3) + 8 (r >> 2)
+        // <= 27, stay below the four the shift drops)
+        auto lane_ok = [&](uint32_t okh, int jq) -> uint32_t { return (jq < p.nq ? okh : 0u) >> (4 * khalf); };
         // mask a half's ineligible rows to +inf (rows (r & 3) + 8 (r >> 2) of its 32)
         auto mask_half = [&](floatx16& A, floatx16& B, uint32_t oa, uint32_t ob) {
             constexpr uint32_t LANE_ROWS = 0x0F0F0F0Fu;
@@ -455,59 +502,84 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             return any;
         };
         const int xs1 = ntile / 8, xs2 = ntile / 4, xs3 = ntile / 2, xs4 = (3 * ntile) / 4;
-        const int ngroups = (ntile + TPS - 1) / TPS;
         // (the previous segment ended with every stage read and every DMA landed)
-        int ops_in_flight = 0;   // this wave's DMA ops of the newest group issued
-        if (ngroups > 0) fill_group(t_begin, 0, ntile);
-        if (ngroups > 1) ops_in_flight = fill_group(t_begin, 1, ntile);
+        // The first two groups at once: nothing to compute beside them yet.
+        const uint64_t p0 = phys(t_begin);   // the first scanned tile (rotated)
+        // corpus tile of tile t (the first: the fill starts there too)
+        uint32_t ct = (uint32_t)p.tile_base + (uint32_t)p0 * ct_step;
+        f_ct = ct;
+        f_dst = dst_first;
+        f_now = ntile < 2 * TPS ? ntile : 2 * TPS;
+        f_left = ntile - f_now;
+        // this wave's DMA ops of the newest group issued (group 1's tiles)
+        const int ops_in_flight = n_ops * (ntile <= TPS ? 0 : ntile < 2 * TPS ? ntile - TPS : TPS);
+#pragma unroll
+        for (int j = 0; j < 2 * TPS; ++j) {
+            if (f_now > 0) {
+#pragma unroll
+                for (int i = 0; i < OPT; ++i) fill_op(i);
+            }
+        }
         vm_wait(ops_in_flight);   // this wave's part of group 0
         block_barrier();          // everyone's
         if (ntile > 0) {
             head(lds, 0);
-            mfma_half(lds, 0, acc00, acc01, [](int) {}, lds, 1);   // H0(0), then the head of H1(0)
-            need_mask = tile_ok(phys(t_begin), okw);
+            mfma_half(lds, 0, acc00, acc01, [](int) {}, no_dma, lds, 1);   // H0(0), then the head of H1(0)
+            need_mask = tile_ok(ct, okw);
         }
         int slot_t = 0;   // LDS slot of tile t
-        // row base of tile t (scalar; wraps with the rotation)
-        uint32_t rbase = (uint32_t)(phys(t_begin) * (uint64_t)p.tile_stride * H_BN);
-        const uint32_t rb_step = (uint32_t)(p.tile_stride * H_BN), rb_wrap = (uint32_t)(p.ntiles * p.tile_stride * H_BN);
-        const uint32_t rb_base = (uint32_t)(p.tile_base * H_BN);   // (rows of the scanned range's first tile)
+        int tj = 0;       // t % TPS
         int xs_next = XS && xs ? xs1 : -1;   // the next cross-slot exchange tile
         for (int t = 0; t < ntile; ++t) {
-            const uint32_t rb0 = rb_base + rbase + 4 * khalf;
-            rbase += rb_step;
-            if (rbase >= rb_wrap) rbase -= rb_wrap;
+            // row base of tile t (scalar; wraps with the rotation)
+            const uint32_t rb0 = ct * (uint32_t)H_BN + 4 * khalf;
+            ct += ct_step;
+            if (ct >= ct_end) ct -= ct_span;
             WV_DBG_COUNT(0)
-            const int g = t / TPS;
             const uint4* img = lds + slot_t * St::U4;
             slot_t = next_slot(slot_t);
             const bool more = t + 1 < ntile;
-            // the group's last tile: group g + 1 landed and every wave is
-            // done with tile t - 1, hence with group g - 1's stage (its last
-            // reads: phase A of that group's last tile); only then is group
-            // g + 2 issued into it -- (g + 2) % 3 = (g - 1) % 3 -- a group's
-            // time ahead of its first read.  (Issued at the start of group g
-            // instead, a wave could overwrite that stage while a slower wave
-            // still ran phase A of group g - 1's last tile.)
-            if (t % TPS == TPS - 1 && g + 1 < ngroups) {
+            // the group's last tile (g = t / TPS, with tiles after it): group
+            // g + 1 landed and every wave is done with tile t - 1, hence with
+            // group g - 1's stage (its last reads: phase A of that group's
+            // last tile); only then is group g + 2 issued into it --
+            // (g + 2) % 3 = (g - 1) % 3 -- a group's time ahead of its first
+            // read.  (Issued at the start of group g instead, a wave could
+            // overwrite that stage while a slower wave still ran phase A of
+            // group g - 1's last tile.)  The burst is handed to the k-steps
+            // of this tile's two halves (dma_steps): every op of it is
+            // issued after this barrier and before the next group barrier,
+            // whose vm_wait(0) covers it.
+            if (tj == TPS - 1 && more) {
                 vm_wait(0);
                 block_barrier();
 #ifndef WV_H16_ABLATE_NO_FILL
-                if (g + 2 < ngroups) fill_group(t_begin, g + 2, ntile);
+                f_now = f_left < TPS ? f_left : TPS;
+                f_left -= f_now;
 #endif
             }
+            tj = tj == TPS - 1 ? 0 : tj + 1;
             // lanes l and l ^ 32 keep lists for the same query column (see the split pass)
             const bool mask_t = need_mask;
-            const uint64_t mo0 = mask_t ? lane_ok(okw, jq0) : 0ull, mo1 = mask_t ? lane_ok(okw, jq1) : 0ull;
             const uint4* nimg = more ? lds + slot_t * St::U4 : img;
             // ---- A: H1(t) MFMAs, H0(t) minima, head of H0(t + 1) ----
-            if (mask_t) mask_half(acc00, acc01, (uint32_t)mo0, (uint32_t)mo1);
+            // (the lane's mask words only when the tile needs them)
+            if (mask_t) mask_half(acc00, acc01, lane_ok((uint32_t)okw, jq0), lane_ok((uint32_t)okw, jq1));
             float m0, m1;
+            // (a scalar test of f_now at each k-step that has an entry)
 #ifdef WV_H16_ABLATE_NO_MIN
             m0 = acc00[0]; m1 = acc01[0];
-            mfma_half(img, 1, acc10, acc11, [](int) {}, nimg, 0);
+            mfma_half(img, 1, acc10, acc11, [](int) {}, dma_steps(0), nimg, 0);
 #else
-            mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), nimg, 0);
+#ifdef WV_H16_FILL_DUP
+            // (two copies of the half, so that the tiles without a burst test
+            // nothing per k-step: + 20 VGPRs at the join, and scratch in the
+            // XS instantiation at NS = 8)
+            if (f_now > 0) mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
+            else mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), no_dma, nimg, 0);
+#else
+            mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
+#endif
 #endif
             // ---- B ----
             bool grew = false;   // a list of this wave changed: thresholds to refresh
@@ -518,15 +590,21 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 grew = extract_half(m0, m1, acc00, acc01, rb0);
             }
             // ---- E: H0(t + 1) MFMAs, H1(t) minima, head of H1(t + 1) ----
-            if (mask_t) mask_half(acc10, acc11, (uint32_t)(mo0 >> 32), (uint32_t)(mo1 >> 32));
+            // (okw is still tile t's: tile t + 1's is read after the half)
+            if (mask_t)
+                mask_half(acc10, acc11, lane_ok((uint32_t)(okw >> 32), jq0), lane_ok((uint32_t)(okw >> 32), jq1));
             if (more) {
+                // (the burst's entries past phase A's k-steps, if any, sit at
+                // fixed k-steps here: a scalar test each)
 #ifdef WV_H16_ABLATE_NO_MIN
                 m0 = acc10[0]; m1 = acc11[0];
-                mfma_half(nimg, 0, acc00, acc01, [](int) {}, nimg, 1);
+                if constexpr (DMA_IN_E) mfma_half(nimg, 0, acc00, acc01, [](int) {}, dma_steps(1), nimg, 1);
+                else mfma_half(nimg, 0, acc00, acc01, [](int) {}, no_dma, nimg, 1);
 #else
-                mfma_half(nimg, 0, acc00, acc01, min_steps(acc10, acc11, m0, m1), nimg, 1);
+                if constexpr (DMA_IN_E) mfma_half(nimg, 0, acc00, acc01, min_steps(acc10, acc11, m0, m1), dma_steps(1), nimg, 1);
+                else mfma_half(nimg, 0, acc00, acc01, min_steps(acc10, acc11, m0, m1), no_dma, nimg, 1);
 #endif
-                need_mask = tile_ok(phys(t_begin + t + 1), okw);
+                need_mask = tile_ok(ct, okw);
             } else {
                 m0 = min16(acc10);
                 m1 = min16(acc11);

@@ -46,6 +46,12 @@ __device__ __forceinline__ void glds4(const void* src, uint32_t lds_wave_base) {
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(src), "s"(lds_wave_base) : "memory");
 }
+// the same from a wave-uniform base + a per-lane 32-bit byte offset
+__device__ __forceinline__ void glds4s(const void* sbase, uint32_t voff, uint32_t lds_wave_base) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_wave_base) : "memory");
+}
 // the same at device scope (sc1: past the CU's L1, so a word other CUs
 // update with atomics is read from L2)
 __device__ __forceinline__ void glds4_dev(const void* src, uint32_t lds_wave_base) {
@@ -96,6 +102,23 @@ __device__ __forceinline__ uint64_t tile_okw(const H16Params& p, uint64_t tile, 
     if (has_allow) okw &= ((cu64*)p.allow)[tl];
     const uint64_t row0 = (uint64_t)tl * H_BN;
     if (row0 + H_BN > p.N) okw &= p.N > row0 ? ((1ull << (p.N - row0)) - 1) : 0ull;
+    return okw;
+}
+
+// The same for a 32-bit tile index the caller keeps as running scalar state
+// (wv_bf_h16_kernel's tile loop): full_tiles = N / H_BN tiles lie wholly below
+// N, so the row-count clip is a 32-bit scalar compare (gfx950 has no scalar
+// ordered 64-bit compare: `row0 + H_BN > N` is a VALU compare a scalar branch
+// then waits for).
+__device__ __forceinline__ uint64_t tile_okw32(const H16Params& p, uint32_t tile, uint32_t full_tiles, bool has_allow) {
+    typedef const __attribute__((address_space(4))) uint64_t cu64;
+    const uint32_t tl = __builtin_amdgcn_readfirstlane(tile);
+    uint64_t okw = ~((cu64*)p.excl)[tl];
+    if (has_allow) okw &= ((cu64*)p.allow)[tl];
+    if (tl >= full_tiles) {
+        const uint64_t row0 = (uint64_t)tl * H_BN;
+        okw &= p.N > row0 ? ((1ull << (p.N - row0)) - 1) : 0ull;
+    }
     return okw;
 }
 

@@ -759,9 +759,23 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
         if (wide) t = std::max<uint64_t>(t, (uint64_t)nqb * std::min<uint64_t>(tiles, (uint64_t)k + 2));
         return (int)std::min<uint64_t>(t, 1u << 30);
     };
-    int sample = wv::H_SAMPLE;   // (WV_H16_SAMPLE: the seed's tile stride, for measurements)
+    // cross-slot threshold (32x32x16 pass, <= 32 list heads per query; on
+    // unless WV_H16_XSLOT=0): 2.87-2.91 vs 2.98-3.00 ms per 1M x 10k key pass
+    const char* xe = std::getenv("WV_H16_XSLOT");
+    const bool xs_on = !xe || std::atoi(xe) != 0;
+    auto xs_fits = [&](const wv::BfSchedule& sc) { return xs_on && !wd && 2 * sc.n_slots <= 32 && k <= 2 * sc.n_slots; };
+    // The seed's tile stride (WV_H16_SAMPLE: for measurements).  Where the
+    // main pass will run the cross-slot exchange, its bounds overtake the
+    // seed's within the first eighth of a segment, so a sparser seed costs
+    // fewer insertion events than its pre-pass saves (H_SAMPLE_XS; the main
+    // pass's schedule does not depend on the stride outside list mode).
+    int sample = wv::H_SAMPLE;
+    if (!wd && !n_dev && !std::getenv("WV_H16_SEED_LISTS") &&
+        xs_fits(wv::bf_schedule(nq, N, target(ntl), bq, tile_rows)))
+        sample = wv::H_SAMPLE_XS;
     if (const char* e = std::getenv("WV_H16_SAMPLE")) sample = std::max(1, std::atoi(e));
-    const bool seed = !wd && ntl >= 64 * (uint64_t)sample && !std::getenv("WV_H16_NO_SEED");
+    // (seeded from H_SEED_MIN_TILES tiles on, whatever the stride)
+    const bool seed = !wd && ntl >= (uint64_t)wv::H_SEED_MIN_TILES && !std::getenv("WV_H16_NO_SEED");
     // The seed pre-pass over 1 / sample of the tiles.  List mode
     // (WV_H16_SEED_LISTS, where its lists fit the seed kernel's one-wave
     // sort; measured slower, profiles/r06/h16_seed_list_mode.log): the
@@ -896,11 +910,8 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     hp.kth = k <= (wd ? 2 * kp : prod * kp) && !seed && !std::getenv("WV_H16_NO_RUNNING")
                  ? k
                  : 0;
-    // cross-slot threshold (32x32x16 pass, <= 32 list heads per query; on
-    // unless WV_H16_XSLOT=0): 2.87-2.91 vs 2.98-3.00 ms per 1M x 10k key pass
-    const char* xe = std::getenv("WV_H16_XSLOT");
-    const bool xs_on = !xe || std::atoi(xe) != 0;
-    if (xs_on && !wd && 2 * sch.n_slots <= 32 && k <= 2 * sch.n_slots) {
+    // cross-slot threshold (xs_fits above)
+    if (xs_fits(sch)) {
         const size_t gb = (size_t)nq * 2 * sch.n_slots * 4;
         HIP_TRY(ix->gslot.ensure(gb));
         HIP_TRY(hipMemsetAsync(ix->gslot.p, 0x7F, gb, s));   // 3.4e38: no head yet

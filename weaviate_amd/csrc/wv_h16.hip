@@ -147,15 +147,39 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     // OPK per k-step from the first k-step on -- one wherever the halves
     // have the k-steps for it (NS >= 3).  Every wave then issues between its
     // own MFMAs instead of all eight at once behind the barrier.
-    constexpr int OPK = (OPT * TPS + 2 * NS - 1) / (2 * NS);
-    static_assert(OPT * TPS <= 2 * NS * OPK, "a burst fits the two halves after its barrier");
-    constexpr bool DMA_IN_E = OPT * TPS > NS * OPK;   // (entries left over for phase E)
+    //
+    // XS: one more entry per group after the fills' (at D = 128: k-step 1 of
+    // phase E), the threshold refresh.  An LDS-DMA of the wave's 64 gtau words
+    // (lane l: query jq0 - l31 + l, clamped for the padding columns, whose
+    // tau stays -inf) into the wave's 256-byte slot after the stages; the
+    // next group barrier's vm_wait(0) covers it, and the words are applied
+    // behind that barrier (tau_apply).  What any slot published to gtau --
+    // the sorting slots' cross-slot bounds (xslot_step) -- so reaches every
+    // slot within two tile groups, with no plain load that would be waited
+    // for behind the tile stream.  Issued on a group's first tile only
+    // (tj_now == 0: the tile that passed the barrier), never in the prologue:
+    // the counted wait there stays the fills' own.
+    constexpr int NENT = OPT * TPS + (XS ? 1 : 0);
+    constexpr int OPK = (NENT + 2 * NS - 1) / (2 * NS);
+    static_assert(NENT <= 2 * NS * OPK, "a burst fits the two halves after its barrier");
+    constexpr bool DMA_IN_E = NENT > NS * OPK;   // (entries left over for phase E)
+    const uint32_t tau_dst = lds0 + (uint32_t)(NSTG * TPS * St::U4 * 16 + 256 * wave);
+    // (an LDS-space pointer: ds_read / ds_write, ordered against the DMA by
+    // the asm statements' memory clobbers like every other read of a stage)
+    typedef __attribute__((address_space(3))) unsigned int lds_u32;
+    lds_u32* tau_lds = (lds_u32*)(reinterpret_cast<unsigned int*>(lds + NSTG * TPS * St::U4) + 64 * wave);
+    uint32_t tau_voff = 0;   // byte offset of this lane's gtau word (per segment)
+    int tj_now = 0;          // (t + 1) % TPS of the tile being computed
     auto dma_steps = [&](int half) {
         return [&, half](int k) {
 #pragma unroll
             for (int o = 0; o < OPK; ++o) {
                 const int e = (half * NS + k) * OPK + o;
-                if (e < OPT * TPS && f_now > 0) fill_op(e % OPT);
+                if (e < OPT * TPS) {
+                    if (f_now > 0) fill_op(e % OPT);
+                } else if (XS && e == OPT * TPS) {
+                    if (tj_now == 0) glds4s_dev<0>(p.gtau, tau_voff, tau_dst);
+                }
             }
         };
     };
@@ -222,6 +246,14 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
 #pragma unroll
         for (int st = 0; st < NS; ++st) asm volatile("" ::"v"(bq0[st].x), "v"(bq1[st].x));
         asm volatile("" ::"v"(tau0), "v"(tau1), "v"(marg0), "v"(marg1));
+        if constexpr (XS) {
+            // the refresh slot starts every segment as "no threshold": the
+            // previous segment's words (all landed behind its last wait) are
+            // another query block's, and the first group barrier reads the
+            // slot before any refresh of this segment was issued
+            tau_lds[lane] = 0xFFFFFFFFu;
+            tau_voff = 4u * (uint32_t)min(jq0 - l31 + lane, p.nq - 1);
+        }
         float l0d[BF_KP], l1d[BF_KP];
         uint32_t l0i[BF_KP], l1i[BF_KP];
 #pragma unroll
@@ -379,6 +411,18 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             pt1 = fminf(__shfl_xor(l1d[BF_KP - 1], 32, 64), tau1);
         };
         refresh_pt();
+        // (XS) the refresh slot's words: gtau of this lane's two queries as
+        // some slot last published them -- read from gtau, hence <= what the
+        // finalize certifies with.  pt is current here (refreshed whenever a
+        // list grew), so min(partner's tail, new tau) = min(pt, new tau): no
+        // shuffle.  The padding columns keep -inf.
+        auto tau_apply = [&] {
+            const unsigned int w0 = tau_lds[l31], w1 = tau_lds[32 + l31];
+            tau0 = fminf(tau0, h16_key_dec(w0));
+            tau1 = fminf(tau1, h16_key_dec(w1));
+            pt0 = fminf(pt0, tau0);
+            pt1 = fminf(pt1, tau1);
+        };
         // running threshold: k of the pair's list entries bound the k-th key
         // (ia from this lane's list, ib from the partner's), + 2 eps
         // (entries picked by select chains over an opaque VGPR index: a
@@ -414,18 +458,33 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             if (jq1 < p.nq) tau1 = fminf(tau1, h16_key_dec(__atomic_load_n(&p.gtau[jq1], __ATOMIC_RELAXED)));
             refresh_pt();
         };
-        const bool running = !SEED && p.kth > 0 && p.gtau != nullptr && !p.xslot;
+        // (never in the XS instantiation, which is launched for p.xslot alone)
+        const bool running = !XS && !SEED && p.kth > 0 && p.gtau != nullptr && !p.xslot;
         // cross-slot threshold: the slots of a query block run side by side
         // over equal tile ranges, so at a fraction f of the segment the heads
         // of all 2 n_slots lists are the minima of disjoint row sets covering
         // f of the corpus; their k-th smallest (+ 2 eps) bounds the k-th key
-        // at rank ~ k / f instead of the seed's ~ k H_SAMPLE.  Stored at 1/8,
-        // 1/4, 1/2 of the segment, read at 1/4, 1/2, 3/4 (the values the
-        // other slots stored one step earlier).  Lane half 0 selects for
-        // jq0, lane half 1 for jq1.
+        // at rank ~ k / f instead of the seed's ~ k H_SAMPLE.  Every slot
+        // stores its heads at 1/16 of the segment and at every eighth from
+        // 1/8 to 7/8; at each point the slots with (slot + point) % XS_SORT
+        // == 0 (all of them below XS_SORT slots: slots 0 .. XS_SORT - 1 exist
+        // otherwise, so every point has a sorter) read all heads, select,
+        // and publish the bound to gtau with atomicMin; the other slots get
+        // it from gtau through the refresh slot (tau_apply) a group or two
+        // later.  A sorter reads what is there -- an unwritten head is
+        // 3.4e38, a stale one still a minimum over rows of the corpus -- and
+        // nothing waits for another slot.  Lane half 0 selects for jq0, lane
+        // half 1 for jq1.
         const bool xs = XS && !SEED && p.kth > 0;   // (its own instantiation: the code costs SGPRs)
-        auto xslot_step = [&](bool rd, bool wr) {
+        auto xslot_step = [&](bool rd) {
             const int nv = 2 * p.n_slots;
+            {
+                const int s2 = 2 * slot + khalf;
+                if (jq0 < p.nq && l0d[0] < FLT_MAX)
+                    __hip_atomic_store(p.gslot + (size_t)jq0 * nv + s2, l0d[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (jq1 < p.nq && l1d[0] < FLT_MAX)
+                    __hip_atomic_store(p.gslot + (size_t)jq1 * nv + s2, l1d[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             if (rd) {
                 const int jq = khalf ? jq1 : jq0;
                 int nvv = jq < p.nq ? nv : 0;   // (opaque VGPR, as ve below)
@@ -468,13 +527,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 tau1 = fminf(tau1, khalf ? b : bo);
                 refresh_pt();
             }
-            if (wr) {
-                const int s2 = 2 * slot + khalf;
-                if (jq0 < p.nq && l0d[0] < FLT_MAX)
-                    __hip_atomic_store(p.gslot + (size_t)jq0 * nv + s2, l0d[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (jq1 < p.nq && l1d[0] < FLT_MAX)
-                    __hip_atomic_store(p.gslot + (size_t)jq1 * nv + s2, l1d[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
         };
         // a half's candidates: the column minima against the thresholds, and
         // (rare) insertion of the column minimum (wv_topk.h min_extract)
@@ -501,7 +553,10 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             }
             return any;
         };
-        const int xs1 = ntile / 8, xs2 = ntile / 4, xs3 = ntile / 2, xs4 = (3 * ntile) / 4;
+        // the cross-slot exchange points: tile ntile / 16, then i ntile / 8,
+        // i = 1 .. 7 (xs_i: the next point's i, 0 for the first)
+        int xs_i = 0;
+        int rd_in = XS_READ_EVERY;   // group barriers until the next refresh read
         // (the previous segment ended with every stage read and every DMA landed)
         // The first two groups at once: nothing to compute beside them yet.
         const uint64_t p0 = phys(t_begin);   // the first scanned tile (rotated)
@@ -529,7 +584,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         }
         int slot_t = 0;   // LDS slot of tile t
         int tj = 0;       // t % TPS
-        int xs_next = XS && xs ? xs1 : -1;   // the next cross-slot exchange tile
+        int xs_next = XS && xs ? ntile / 16 : -1;   // the next cross-slot exchange tile
         for (int t = 0; t < ntile; ++t) {
             // row base of tile t (scalar; wraps with the rotation)
             const uint32_t rb0 = ct * (uint32_t)H_BN + 4 * khalf;
@@ -557,8 +612,18 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 f_now = f_left < TPS ? f_left : TPS;
                 f_left -= f_now;
 #endif
+                // the group's threshold refresh: the words the last group's
+                // DMA brought (landed: the wait above), before this group's
+                // is issued into the slot
+                if constexpr (XS) {
+                    if (XS_READ_EVERY == 1 || --rd_in == 0) {
+                        tau_apply();
+                        rd_in = XS_READ_EVERY;
+                    }
+                }
             }
             tj = tj == TPS - 1 ? 0 : tj + 1;
+            tj_now = tj;
             // lanes l and l ^ 32 keep lists for the same query column (see the split pass)
             const bool mask_t = need_mask;
             const uint4* nimg = more ? lds + slot_t * St::U4 : img;
@@ -619,9 +684,12 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 else if (grew) refresh_pt();
                 if constexpr (XS) {
                     if (t == xs_next) {
-                        xslot_step(t != xs1, t != xs4);
+                        xslot_step(XS_SORT <= 1 || p.n_slots < XS_SORT || ((slot + xs_i) & (XS_SORT - 1)) == 0);
                         // (equal points of a short segment collapse into one step)
-                        xs_next = t < xs2 && xs2 > t ? xs2 : t < xs3 && xs3 > t ? xs3 : t < xs4 && xs4 > t ? xs4 : -1;
+                        do {
+                            ++xs_i;
+                            xs_next = xs_i < 8 ? (xs_i * ntile) >> 3 : -1;
+                        } while (xs_i < 8 && xs_next <= t);
                     }
                 }
             }
@@ -1449,7 +1517,10 @@ hipError_t wv_launch_bf_h16(const wv::H16Params* p, int ns, int seed, hipStream_
         return hipErrorInvalidValue;
     const bool l2 = p->metric == WV_METRIC_L2;
     if (l2 && !p->xns) return hipErrorInvalidValue;
-    const size_t lds = (size_t)wv::H_STAGES * wv::H_TPS8 * (2 * ns * 64 + 17) * 16;
+    // the stages, and (XS) the waves' threshold refresh slots after them
+    const size_t lds = (size_t)wv::H_STAGES * wv::H_TPS8 * (2 * ns * 64 + 17) * 16 +
+                       (!seed && p->xslot ? (size_t)wv::H_XS_LDS : 0);
+    if (!seed && p->xslot && (!p->gtau || !p->gslot || !p->marg || p->kth < 1)) return hipErrorInvalidValue;
 #define WV_H16_GO(NS, L, S)                                                                                    \
     if (!S && p->xslot)                                                                                        \
         hipLaunchKernelGGL((wv::wv_bf_h16_kernel<NS, L, false, true>), dim3(nb), dim3(512), lds, s, *p);       \

@@ -134,5 +134,20 @@ struct H16Stage {
 #endif
 constexpr int H_TPS8 = WV_H16_TPS;   // tiles per LDS stage (8-wave kernel): one barrier per H_TPS8 tiles
 constexpr int H_STAGES = 3;   // a stage holds H_TPS tiles; stage p % 3 computes while p + 1, p + 2 land
+// The cross-slot exchange of the 8-wave kernel (XS): one slot in XS_SORT
+// sorts the list heads at an exchange point (a power of two; 1: every slot),
+// and every slot reads its refresh slot at every XS_READ_EVERY-th group
+// barrier.  (Defines for A/B builds; the measured choices: DESIGN §3.2.)
+#ifndef WV_H16_XS_SORT
+#define WV_H16_XS_SORT 4
+#endif
+#ifndef WV_H16_XS_READ_EVERY
+#define WV_H16_XS_READ_EVERY 1
+#endif
+constexpr int XS_SORT = WV_H16_XS_SORT;
+constexpr int XS_READ_EVERY = WV_H16_XS_READ_EVERY;
+static_assert(XS_SORT >= 1 && (XS_SORT & (XS_SORT - 1)) == 0 && XS_READ_EVERY >= 1, "see above");
+// bytes of LDS after the stages in the XS instantiation: 64 gtau words per wave
+constexpr int H_XS_LDS = 8 * 256;
 
 }  // namespace wv

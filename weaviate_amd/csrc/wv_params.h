@@ -122,6 +122,8 @@ constexpr int H_BQ = 512;     // queries per block: 64 per wave, held in registe
 constexpr int H_PROD = 2;     // lists per query per slot (the two lane halves)
 constexpr int H_NS_MAX = 8;   // 16-k steps: D <= 128
 constexpr int H_SAMPLE = 16;  // seed pre-pass: every H_SAMPLE-th tile
+constexpr int H_SAMPLE_XS = 32;   // the same where the main pass runs the cross-slot exchange
+constexpr int H_SEED_MIN_TILES = 1024;   // corpora of fewer tiles run without the seed pre-pass
 
 #if defined(__HIPCC__)
 __host__ __device__

@@ -205,6 +205,31 @@ int wv_search_batch(wv_index *ix, const float *queries, int nq, int k, int ef, c
                     uint64_t allow_nbits, uint64_t allow_stride_words, int mode, uint64_t *out_ids,
                     float *out_dists, int32_t *out_n);
 
+/* wv_search_batch with one allow list per query, as ids: query q may return only
+ * allow_ids[allow_offsets[q] .. allow_offsets[q+1]) -- local ids, strictly
+ * ascending within a query (the AllowList's Slice()).  An empty range allows
+ * nothing.  Result and order are those of wv_search_batch given per-query
+ * bitmaps with exactly those bits set.  All pointers are host memory and the
+ * call blocks.  An id past the rows is skipped (flat_search.go:29-35), not an
+ * error; offsets that do not start at 0 or decrease, and ids that do not
+ * ascend, return WV_EINVAL.  Flat or HNSW is decided per query on the host
+ * from the list's length (AUTO: search.go:64-79; EXACT: flat; HNSW: HNSW).  A
+ * flat query is answered by the sparse kernel, which reads only the listed
+ * rows (flat_search.go:24-58), unless the index is PQ-compressed, k > 256, a
+ * vector is wider than 8192 floats or, in EXACT mode, the list holds an
+ * eighth of the rows or more; those and the HNSW queries run as
+ * wv_search_batch over bitmap rows built on the device. */
+int wv_search_batch_ids(wv_index *ix, const float *queries, int nq, int k, int ef, const uint64_t *allow_ids,
+                        const uint64_t *allow_offsets /* [nq+1] */, int mode, uint64_t *out_ids, float *out_dists,
+                        int32_t *out_n);
+/* The last wv_search_batch_ids on the index (nullable outputs): queries answered
+ * by the sparse flat kernel, ids handed to it, queries sent down the bitmap route. */
+int wv_last_sparse_stats(wv_index *ix, uint64_t *sparse_queries, uint64_t *sparse_ids, uint64_t *bitmap_queries);
+/* The sparse flat kernel's device time in the last wv_search_batch_ids
+ * (milliseconds, chunk merge included; 0 when it did not run or timing is
+ * off, wv_index_set_timing).  A measurement hook. */
+int wv_last_sparse_time(wv_index *ix, float *kernel_ms);
+
 /* Device-resident variant: every pointer is device memory.  d_queries holds
  * nq rows at a stride of wv_index_query_ld(ix) floats (dim rounded up to 4;
  * the pad columns are ignored).  The work is queued on `stream` (a
@@ -333,9 +358,13 @@ int wv_batcher_search(wv_batcher *b, const float *vector, int k, const uint64_t 
                       uint64_t *out_ids, float *out_dists, int32_t *out_n);
 /* The same with the AllowList as strictly ascending ids (its Slice(),
  * helpers/allow_list.go:19-118): filtered == 0 means no list; filtered with
- * n_allow == 0 allows nothing.  The ids go straight into the batch's bitmap
- * row (no per-caller dense bitmap); a batch whose requests all carry the
- * same list sends it once. */
+ * n_allow == 0 allows nothing.  A batch whose requests all carry the same
+ * list sends it once, as one shared bitmap (compacted on the device); a batch
+ * of id lists that differ goes to wv_search_batch_ids as ids, with no bitmap
+ * row filled on the host (WV_BATCHER_IDS=0, read when the batcher is created:
+ * bitmap rows as before, for A/B runs).  A batch that mixes id lists with
+ * bitmap requests, and every batch of a group batcher, fills one bitmap row
+ * per request. */
 int wv_batcher_search_ids(wv_batcher *b, const float *vector, int k, int filtered, const uint64_t *allow_ids,
                           uint64_t n_allow, uint64_t *out_ids, float *out_dists, int32_t *out_n);
 /* SearchByVectorDistance through the micro-batcher: concurrent callers with

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/wvgpu.h"
@@ -80,6 +81,9 @@ hipError_t wv_launch_h16_margin(int metric, int D, const float* qnorm, const flo
 hipError_t wv_launch_h16_gtau(const unsigned int* gtau, int nq, float sx, const float* qscale, float* tau,
                               hipStream_t s);
 float wv_h16_pow2_scale(float maxabs);
+hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s);
+hipError_t wv_launch_ids_to_bits(const uint32_t* ids, const uint64_t* off, const int32_t* sel, int nsel,
+                                 uint64_t max_len, uint64_t n_rows, uint64_t words, uint64_t* bits, hipStream_t s);
 hipError_t wv_launch_pq_topk(const float* skey, const uint32_t* sval, const float* dist, const uint32_t* rows,
                              uint64_t nr, int q0, int nqc, int k, uint64_t id_base, uint64_t* out_ids, float* out_d,
                              int32_t* out_n, hipStream_t s);
@@ -369,6 +373,13 @@ struct wv_index {
     // f16 key pass over a compacted shared allow list: the rows' image,
     // their |x|^2 and the scan's exclusion bits (the last tile's padding)
     DevBuf cimg16, cxnorm, cexcl;
+    // wv_search_batch_ids: the lists (u32 ids, offsets), the rows of each
+    // route, the sparse kernel's per-chunk keys, and the bitmap route's
+    // gathered queries, bitmap rows and results
+    DevBuf fi_ids, fi_off, fi_sel, fi_part, fi_q, fi_bits, fi_oid, fi_od, fi_on;
+    uint64_t fi_sparse_q = 0, fi_sparse_ids = 0, fi_bitmap_q = 0;   // the last call's routes
+    hipEvent_t fi_ev[2] = {nullptr, nullptr};                       // the sparse kernel (timing on)
+    bool fi_timed = false;
 };
 
 namespace {
@@ -1880,6 +1891,11 @@ int wv_index_destroy(wv_index* ix) {
     ix->cimg16.release();
     ix->cxnorm.release();
     ix->cexcl.release();
+    for (DevBuf* b : {&ix->fi_ids, &ix->fi_off, &ix->fi_sel, &ix->fi_part, &ix->fi_q, &ix->fi_bits, &ix->fi_oid,
+                      &ix->fi_od, &ix->fi_on})
+        b->release();
+    for (auto e : ix->fi_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto& sl : ix->slots) {
         if (sl.pin) (void)hipHostFree(sl.pin);
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -2719,6 +2735,245 @@ int wv_search_batch(wv_index* ix, const float* queries, int nq, int k, int ef, c
     std::memcpy(out_ids, pin + o_i, ib);
     std::memcpy(out_dists, pin + o_d, db);
     std::memcpy(out_n, pin + o_n, nb);
+    return WV_OK;
+}
+
+// wv_search_batch with one allow list per query, as ids.  The flat-versus-HNSW
+// rule of search.go:64-79 is applied on the host from each list's length; a
+// flat query whose list is short goes to the sparse kernel (wv_flat_ids.hip),
+// every other query to search_core over bitmap rows scattered on the device.
+int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int ef, const uint64_t* allow_ids,
+                        const uint64_t* allow_offsets, int mode, uint64_t* out_ids, float* out_dists, int32_t* out_n) {
+    if (nq < 0) return fail(WV_EINVAL, "wv_search_batch_ids: nq < 0");
+    if (k <= 0) return fail(WV_EINVAL, "wv_search_batch_ids: k <= 0");
+    if (!allow_offsets) return fail(WV_EINVAL, "wv_search_batch_ids: null allow_offsets");
+    if (check(ix)) return fail(WV_EINVAL, "wv_search_batch_ids: null index");
+    if (nq && (!queries || !out_ids || !out_dists || !out_n))
+        return fail(WV_EINVAL, "wv_search_batch_ids: null queries or outputs");
+    if (allow_offsets[0] != 0) return fail(WV_EINVAL, "wv_search_batch_ids: allow_offsets[0] must be 0");
+    for (int q = 0; q < nq; ++q)
+        if (allow_offsets[q + 1] < allow_offsets[q])
+            return fail(WV_EINVAL, "wv_search_batch_ids: allow_offsets must not decrease");
+    const uint64_t total = allow_offsets[nq];
+    if (total && !allow_ids) return fail(WV_EINVAL, "wv_search_batch_ids: null allow_ids");
+    if (nq == 0) return WV_OK;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t qb = (size_t)nq * ix->dim * 4, lb = (size_t)total * 4, fb = ((size_t)nq + 1) * 8,
+                 ib = (size_t)nq * k * 8, db = (size_t)nq * k * 4, nb = (size_t)nq * 4;
+    const size_t o_l = al(qb), o_f = o_l + al(lb), o_i = o_f + al(fb), o_d = o_i + al(ib), o_n = o_d + al(db),
+                 need = o_n + al(nb);
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    SlotLease lease(ix);
+    wv_index::HostSlot& sl = *lease.sl;
+    if (sl.cap < need) {
+        if (sl.pin) HIP_TRY(hipHostFree(sl.pin));
+        sl.pin = nullptr;
+        sl.cap = 0;
+        const size_t want = std::max<size_t>(need + need / 4, 1 << 20);
+        HIP_TRY(hipHostMalloc(&sl.pin, want, hipHostMallocDefault));
+        sl.cap = want;
+    }
+    if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    char* pin = static_cast<char*>(sl.pin);
+    std::memcpy(pin, queries, qb);
+    // ids narrowed to u32 (capacity < 2^31; larger ids name no row)
+    uint32_t* ids32 = reinterpret_cast<uint32_t*>(pin + o_l);
+    uint64_t* off = reinterpret_cast<uint64_t*>(pin + o_f);
+    // In an ascending list the ids >= 2^31 are a suffix: each list's kept
+    // length first (a list out of order is refused below, whatever was kept)
+    uint64_t pos = 0;
+    for (int q = 0; q < nq; ++q) {
+        off[q] = pos;
+        uint64_t m = allow_offsets[q + 1] - allow_offsets[q];
+        while (m && allow_ids[allow_offsets[q] + m - 1] >= (1ull << 31)) --m;
+        pos += m;
+    }
+    off[nq] = pos;
+    // one pass over the lists: the ascending check and the narrowing, in
+    // threads over equal shares of the ids when the batch is large (a 256 x
+    // 40,000 batch reads 80 MB: one core's pass cost more than the search)
+    auto narrow = [&](int q0, int q1) {
+        uint64_t bad = 0;
+        for (int q = q0; q < q1; ++q) {
+            const uint64_t* a = allow_ids + allow_offsets[q];
+            const uint64_t n = allow_offsets[q + 1] - allow_offsets[q], m = off[q + 1] - off[q];
+            uint32_t* o = ids32 + off[q];
+            for (uint64_t i = 0; i < m; ++i) o[i] = (uint32_t)a[i];
+            for (uint64_t i = 1; i < n; ++i) bad |= (uint64_t)(a[i] <= a[i - 1]);
+        }
+        return bad != 0;
+    };
+    bool bad = false;
+    const int nth = (int)std::min<uint64_t>(std::min(8, nq), total >> 18);
+    if (nth <= 1) {
+        bad = narrow(0, nq);
+    } else {
+        std::vector<std::thread> th;
+        std::vector<char> tb((size_t)nth, 0);
+        int q0 = 0;
+        for (int t = 0; t < nth; ++t) {
+            int q1 = q0;
+            const uint64_t until = t == nth - 1 ? total : total / nth * (t + 1);
+            while (q1 < nq && (allow_offsets[q1 + 1] <= until || t == nth - 1)) ++q1;
+            th.emplace_back([&, t, q0, q1] { tb[t] = narrow(q0, q1); });
+            q0 = q1;
+        }
+        for (auto& x : th) x.join();
+        for (char c : tb) bad |= c != 0;
+    }
+    if (bad) return fail(WV_EINVAL, "wv_search_batch_ids: allow ids must be strictly ascending within a query");
+    {
+        std::lock_guard<std::mutex> g(ix->mu);
+        HIP_TRY(hipSetDevice(ix->cfg.device));
+        hipStream_t s = ix->stream;
+        const float* dq = nullptr;
+        int rc = stage_queries(ix, reinterpret_cast<const float*>(pin), nq, &dq, s);
+        if (rc) return rc;
+        HIP_TRY(ix->fi_ids.ensure(std::max<size_t>(pos * 4, 4)));
+        HIP_TRY(ix->fi_off.ensure(fb));
+        if (pos) HIP_TRY(hipMemcpyAsync(ix->fi_ids.p, ids32, pos * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ix->fi_off.p, off, fb, hipMemcpyHostToDevice, s));
+        HIP_TRY(ix->out_ids.ensure(ib));
+        HIP_TRY(ix->out_d.ensure(db));
+        HIP_TRY(ix->out_n.ensure(nb));
+        rc = refresh_bitmaps(ix);
+        if (rc) return rc;
+        // the route of every query, from its list's length
+        const uint64_t N = ix->n_rows;
+        const int ef_eff = ef <= 0 ? search_time_ef(ix->cfg, k) : ef;
+        const bool can_hnsw = ix->has_graph && ef_eff <= wv::HNSW_EF_MAX;
+        const bool sparse_ok = !ix->pq_on && k <= wv::BF_WIDE_KMAX && ix->dpad <= wv::FLAT_IDS_DPAD_MAX;
+        std::vector<int32_t> sel[3];   // sparse, bitmap rows searched flat, bitmap rows searched by HNSW
+        uint64_t sp_ids = 0, sp_max = 0;
+        for (int q = 0; q < nq; ++q) {
+            const uint64_t L = allow_offsets[q + 1] - allow_offsets[q];
+            bool flat;
+            if (mode == WV_MODE_EXACT) flat = true;
+            else if (mode == WV_MODE_HNSW) flat = false;
+            else flat = !can_hnsw || (!ix->cfg.forbid_flat && (int64_t)L < ix->cfg.flat_search_cutoff);
+            // (EXACT: the 1/8 rule of run_exact's compacted scans)
+            const bool sparse = flat && sparse_ok && (mode != WV_MODE_EXACT || 8 * L < N);
+            sel[sparse ? 0 : flat ? 1 : 2].push_back(q);
+            if (sparse) {
+                sp_ids += L;
+                sp_max = std::max(sp_max, off[q + 1] - off[q]);
+            }
+        }
+        std::vector<int32_t> order;
+        for (auto& v : sel) order.insert(order.end(), v.begin(), v.end());
+        HIP_TRY(ix->fi_sel.ensure(nb));
+        HIP_TRY(hipMemcpyAsync(ix->fi_sel.p, order.data(), nb, hipMemcpyHostToDevice, s));
+        ix->fi_sparse_q = sel[0].size();
+        ix->fi_sparse_ids = sp_ids;
+        ix->fi_bitmap_q = sel[1].size() + sel[2].size();
+        ix->fi_timed = false;
+        if (!sel[0].empty()) {
+            const int ns = (int)sel[0].size();
+            // chunks of a list: enough workgroups to fill the machine, at
+            // least 512 ids each; whole wave rounds (256 ids)
+            uint64_t nc = std::max<uint64_t>(1, (2 * (uint64_t)ix->n_cus + ns - 1) / ns);
+            nc = std::max<uint64_t>(1, std::min(nc, (sp_max + 511) / 512));
+            const uint64_t chunk_len = std::max<uint64_t>(256, ((sp_max + nc - 1) / nc + 255) / 256 * 256);
+            nc = std::max<uint64_t>(1, (sp_max + chunk_len - 1) / chunk_len);
+            wv::FlatIdsParams fp{};
+            fp.X = ix->vecs.as<float>();
+            fp.Q = dq;
+            fp.excl = ix->excl.as<uint64_t>();
+            fp.excl_nbits = ix->capacity;
+            fp.ids = ix->fi_ids.as<uint32_t>();
+            fp.off = ix->fi_off.as<uint64_t>();
+            fp.sel = ix->fi_sel.as<int32_t>();
+            fp.n_rows = N;
+            fp.id_base = ix->cfg.id_base;
+            fp.chunk_len = chunk_len;
+            fp.ns = ns;
+            fp.n_chunks = (int)nc;
+            if (nc > 1) {
+                HIP_TRY(ix->fi_part.ensure((size_t)ns * nc * k * 8));
+                fp.part = ix->fi_part.as<unsigned long long>();
+            }
+            fp.D = ix->dim;
+            fp.dpad = ix->dpad;
+            fp.ldx = ix->ldx;
+            fp.metric = ix->metric;
+            fp.k = k;
+            fp.out_ids = ix->out_ids.as<uint64_t>();
+            fp.out_d = ix->out_d.as<float>();
+            fp.out_n = ix->out_n.as<int32_t>();
+            if (ix->timing) {
+                for (auto& e : ix->fi_ev)
+                    if (!e) HIP_TRY(hipEventCreate(&e));
+                HIP_TRY(hipEventRecord(ix->fi_ev[0], s));
+            }
+            HIP_TRY(wv_launch_flat_ids(&fp, s));
+            if (ix->timing) {
+                HIP_TRY(hipEventRecord(ix->fi_ev[1], s));
+                ix->fi_timed = true;
+            }
+        }
+        // the bitmap route: rows scattered from the ids into bounded scratch,
+        // then today's kernels (search_core) and each row back to its query
+        const uint64_t words = std::max<uint64_t>(1, (N + 63) / 64);
+        const size_t rows_cap = (size_t)std::max<uint64_t>(1, std::min<uint64_t>(65535, (1ull << 30) / (words * 8)));
+        size_t base = sel[0].size();
+        for (int grp = 1; grp <= 2; ++grp) {
+            const std::vector<int32_t>& v = sel[grp];
+            for (size_t c0 = 0; c0 < v.size(); c0 += rows_cap) {
+                const int n = (int)std::min(rows_cap, v.size() - c0);
+                const int32_t* d_sel = ix->fi_sel.as<int32_t>() + base + c0;
+                uint64_t max_len = 0;
+                for (int i = 0; i < n; ++i) max_len = std::max(max_len, off[v[c0 + i] + 1] - off[v[c0 + i]]);
+                HIP_TRY(ix->fi_q.ensure((size_t)n * ix->dpad * 4));
+                HIP_TRY(ix->fi_bits.ensure((size_t)n * words * 8));
+                HIP_TRY(ix->fi_oid.ensure((size_t)n * k * 8));
+                HIP_TRY(ix->fi_od.ensure((size_t)n * k * 4));
+                HIP_TRY(ix->fi_on.ensure((size_t)n * 4));
+                hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(128), 0, s, dq, ix->dpad, d_sel, n, ix->dpad,
+                                   ix->fi_q.as<float>(), ix->dpad);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemsetAsync(ix->fi_bits.p, 0, (size_t)n * words * 8, s));
+                HIP_TRY(wv_launch_ids_to_bits(ix->fi_ids.as<uint32_t>(), ix->fi_off.as<uint64_t>(), d_sel, n, max_len, N,
+                                              words, ix->fi_bits.as<uint64_t>(), s));
+                rc = search_core(ix, ix->fi_q.as<float>(), n, k, ef, ix->fi_bits.as<uint64_t>(), std::max<uint64_t>(N, 1),
+                                 words, grp == 1 ? WV_MODE_EXACT : WV_MODE_HNSW, ix->fi_oid.as<uint64_t>(),
+                                 ix->fi_od.as<float>(), ix->fi_on.as<int32_t>(), s);
+                if (rc) return rc;
+                hipLaunchKernelGGL(scatter_results_kernel, dim3(n), dim3(64), 0, s, ix->fi_oid.as<uint64_t>(),
+                                   ix->fi_od.as<float>(), ix->fi_on.as<int32_t>(), d_sel, n, k,
+                                   ix->out_ids.as<uint64_t>(), ix->out_d.as<float>(), ix->out_n.as<int32_t>());
+                HIP_TRY(hipGetLastError());
+            }
+            base += v.size();
+        }
+        HIP_TRY(hipMemcpyAsync(pin + o_i, ix->out_ids.p, ib, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(pin + o_d, ix->out_d.p, db, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(pin + o_n, ix->out_n.p, nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(sl.done, s));
+    }
+    HIP_TRY(hipEventSynchronize(sl.done));
+    std::memcpy(out_ids, pin + o_i, ib);
+    std::memcpy(out_dists, pin + o_d, db);
+    std::memcpy(out_n, pin + o_n, nb);
+    return WV_OK;
+}
+
+int wv_last_sparse_stats(wv_index* ix, uint64_t* sparse_queries, uint64_t* sparse_ids, uint64_t* bitmap_queries) {
+    if (check(ix)) return fail(WV_EINVAL, "wv_last_sparse_stats: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (sparse_queries) *sparse_queries = ix->fi_sparse_q;
+    if (sparse_ids) *sparse_ids = ix->fi_sparse_ids;
+    if (bitmap_queries) *bitmap_queries = ix->fi_bitmap_q;
+    return WV_OK;
+}
+
+int wv_last_sparse_time(wv_index* ix, float* kernel_ms) {
+    if (check(ix) || !kernel_ms) return fail(WV_EINVAL, "wv_last_sparse_time: bad argument");
+    std::lock_guard<std::mutex> g(ix->mu);
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    *kernel_ms = 0.f;
+    if (!ix->fi_timed) return WV_OK;
+    HIP_TRY(hipEventSynchronize(ix->fi_ev[1]));
+    HIP_TRY(hipEventElapsedTime(kernel_ms, ix->fi_ev[0], ix->fi_ev[1]));
     return WV_OK;
 }
 

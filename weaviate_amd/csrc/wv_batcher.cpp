@@ -14,8 +14,10 @@
 // (allow_stride_words), so the AUTO dispatch of search.go:64-79 (flat vs HNSW
 // by allowList.Len()) is still decided per query inside the batch.  An allow
 // list crosses as a bitmap or as ascending ids (the AllowList's Slice(),
-// helpers/allow_list.go:19-118), written straight into the batch's row; a
-// group whose requests all carry the same list sends it once (shared).
+// helpers/allow_list.go:19-118); a group whose requests all carry the same
+// list sends it once (shared), a group of id lists that differ is sent as ids
+// (wv_search_batch_ids: the device walks only the listed rows), and any other
+// filtered group writes each request's list into the batch's bitmap rows.
 //
 // Dispatch is latency-first ("natural batching"): one batch runs on the device
 // at a time, and a free worker takes EVERY request queued meanwhile the moment
@@ -119,7 +121,7 @@ struct Staging {
     std::vector<Request*> take, g;
     std::vector<char> used;
     std::vector<float> q, ds, tg;
-    std::vector<uint64_t> bits, ids;
+    std::vector<uint64_t> bits, ids, lists, offs;   // (lists / offs: a group sent as id lists)
     std::vector<int32_t> cnt;
     std::vector<int64_t> cnt64;
     int64_t cap = 0;    // (distance groups) entries per query in ids / ds
@@ -134,6 +136,7 @@ struct wv_batcher {
     int max_batch = 256;
     int max_wait_us = 0;
     int refill_gap_us = REFILL_GAP_US;
+    bool send_ids = true;   // id lists that differ go out as ids (WV_BATCHER_IDS=0: as bitmap rows)
     std::mutex mu;
     std::condition_variable cv_work;
     std::deque<Request*> queue;
@@ -184,6 +187,27 @@ struct wv_batcher {
         if (filtered) {
             bool shared = true;
             for (int i = 1; i < n && shared; ++i) shared = same_list(s.g[0], s.g[i]);
+#ifndef WV_TSAN_BUILD
+            // id lists of the requests' own: sent as ids, so the device walks
+            // only the listed rows (flat_search.go:24-58) and no bitmap row
+            // is filled here.  (The ThreadSanitizer build's CPU index has no
+            // such entry point.)
+            bool all_ids = send_ids && !shared && !grp && !s.g[0]->dist;
+            for (int i = 0; i < n && all_ids; ++i) all_ids = s.g[i]->allow == nullptr;
+            if (all_ids) {
+                s.offs.assign((size_t)n + 1, 0);
+                for (int i = 0; i < n; ++i) s.offs[i + 1] = s.offs[i] + s.g[i]->n_ids;
+                s.lists.resize(s.offs[n]);
+                for (int i = 0; i < n; ++i)
+                    if (s.g[i]->n_ids)
+                        std::memcpy(s.lists.data() + s.offs[i], s.g[i]->allow_ids, s.g[i]->n_ids * 8);
+                s.ids.resize((size_t)n * k);
+                s.ds.resize((size_t)n * k);
+                s.cnt.resize(n);
+                return wv_search_batch_ids(ix, s.q.data(), n, k, 0, s.lists.data(), s.offs.data(), WV_MODE_AUTO,
+                                           s.ids.data(), s.ds.data(), s.cnt.data());
+            }
+#endif
             for (Request* r : s.g) nbits = std::max(nbits, nbits_of(r));
             nbits = std::max<uint64_t>(nbits, 1);   // (an empty list allows nothing)
             const uint64_t words = (nbits + 63) / 64;
@@ -340,6 +364,7 @@ static int create_batcher(wv_index* ix, wv_group* grp, int dim, int max_batch, i
     b->max_batch = max_batch;
     b->max_wait_us = max_wait_us;
     if (const char* e = std::getenv("WV_BATCHER_REFILL_GAP_US")) b->refill_gap_us = std::atoi(e);
+    if (const char* e = std::getenv("WV_BATCHER_IDS")) b->send_ids = std::atoi(e) != 0;
     for (int w = 0; w < 2; ++w) b->th.emplace_back([b, w] { b->loop(b->st[w]); });
     *out = b;
     return WV_OK;

@@ -426,6 +426,28 @@ struct SbdParams {
     unsigned int* cnt;        // [nq][3]: |Q|, A (d <= target), n (rows searchable)
 };
 
+// Flat search over per-query id lists (wv_flat_ids.hip; flat_search.go:24-58):
+// sparse query s is batch row sel[s], its list ids[off[sel[s]] .. off[sel[s] + 1])
+struct FlatIdsParams {
+    const float* X;
+    const float* Q;           // [nq][dpad] (normalized if cosine)
+    const uint64_t* excl;     // tombstone | nil node | no vector
+    uint64_t excl_nbits;
+    const uint32_t* ids;      // every query's list, ascending within a query
+    const uint64_t* off;      // [nq + 1] into ids
+    const int32_t* sel;       // [ns] batch rows the kernel answers
+    uint64_t n_rows;          // ids >= n_rows are skipped
+    uint64_t id_base;
+    uint64_t chunk_len;       // ids per workgroup (a multiple of 128)
+    unsigned long long* part; // [ns][n_chunks][k] sorted keys (n_chunks > 1)
+    int ns, n_chunks;
+    int D, dpad, ldx, metric, k;
+    uint64_t* out_ids;        // [nq][k], row sel[s]
+    float* out_d;
+    int32_t* out_n;
+};
+constexpr int FLAT_IDS_DPAD_MAX = 8192;   // the query row lives in LDS
+
 // Flat search over PQ codes (flat_search.go:19-74 on a compressed index):
 // distances of a chunk of queries against a row list, keyed for a stable
 // segmented sort by (dist, row).

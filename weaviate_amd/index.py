@@ -338,6 +338,40 @@ class GPUVectorIndex:
                                     _ptr(ds), _ptr(n)))
         return ids, ds, n
 
+    def search_batch_ids(self, queries, k: int, allow_ids, ef: int = 0, mode: str = "auto"):
+        """search_batch with one allow list per query given as ids (a sequence
+        of nq integer arrays, each strictly ascending; the AllowList's Slice()):
+        short lists are searched by walking only the listed rows
+        (wv_search_batch_ids).  Same result as search_batch."""
+        qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = qs.shape[0]
+        lists = [np.asarray(a, dtype=np.uint64).reshape(-1) for a in allow_ids]
+        if len(lists) != nq:
+            raise WvError(1, f"allow_ids must hold one id list per query: {len(lists)} vs {nq}")
+        off = np.zeros(nq + 1, np.uint64)
+        if nq:
+            off[1:] = np.cumsum([a.size for a in lists], dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint64), dtype=np.uint64)
+        ids = np.zeros((nq, k), np.uint64)
+        ds = np.zeros((nq, k), np.float32)
+        n = np.zeros(nq, np.int32)
+        check(lib().wv_search_batch_ids(self._h, _ptr(qs), nq, k, ef, _ptr(flat), _ptr(off), _MODES[mode], _ptr(ids),
+                                        _ptr(ds), _ptr(n)))
+        return ids, ds, n
+
+    def last_sparse_stats(self):
+        """The last search_batch_ids: queries the sparse flat kernel answered,
+        the ids handed to it, and the queries that took the bitmap route."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().wv_last_sparse_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"sparse_queries": a.value, "sparse_ids": b.value, "bitmap_queries": c.value}
+
+    def last_sparse_time(self) -> float:
+        """Device milliseconds of the sparse flat kernel in the last search_batch_ids (set_timing on)."""
+        t = C.c_float()
+        check(lib().wv_last_sparse_time(self._h, C.byref(t)))
+        return t.value
+
     def search_batch_device(self, q_ptr: int, nq: int, k: int, out_ids_ptr: int, out_d_ptr: int, out_n_ptr: int,
                             ef: int = 0, allow_ptr: int = 0, allow_nbits: int = 0, allow_stride: int = 0,
                             mode: str = "exact", stream: int = 0):

@@ -115,7 +115,9 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     // LDS address, and the tiles left.  An op's source is X or xns + that
     // index x a tile's bytes -- a shift at D = 128.  (Running 64-bit
     // pointers instead, with their steps and spans, held ten more SGPRs over
-    // the loop: + 8 spill lanes in the D = 128 instantiations.)
+    // the loop: + 8 spill lanes in the D = 128 instantiations.  The two
+    // bases formed once per fetched tile and kept in two SGPR pairs: fewer
+    // scalar instructions per op, measured slower -- DESIGN 3.2.)
     constexpr int NIMG = St::IMG_U4 / 64 > WAVES ? 2 : 1;
     static_assert(St::IMG_U4 / 64 <= 2 * WAVES, "a wave moves at most two image KiB per tile");
     constexpr int OPT = NIMG + (L2 ? 1 : 0);
@@ -125,23 +127,22 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     const uint32_t dst_first = lds0 + (uint32_t)(wave * 1024), dst_end = dst_first + (uint32_t)(NSTG * TPS * St::U4 * 16);
     uint32_t f_ct = 0, f_dst = dst_first;
     int f_left = 0;   // tiles of the segment not handed to a burst yet
-    int f_now = 0;    // tiles of the burst being issued
-    auto fill_op = [&](int i) {
-        if (i < NIMG) {
-            if (wave + WAVES * i < St::IMG_U4 / 64)
-                glds16s(uniform_ptr(X + (uint64_t)f_ct * St::IMG_U4), voff + (uint32_t)(i * WAVES * 1024),
-                        f_dst + (uint32_t)(i * WAVES * 1024));
-        } else if (wave == 0) {
-            glds4s(uniform_ptr(p.xns + (uint64_t)f_ct * H_BN), (uint32_t)(lane * 4), f_dst + St::IMG_U4 * 16);
-        }
-        if (i == OPT - 1) {   // the tile's last entry: on to the next tile
-            f_ct += ct_step;
-            if (f_ct >= ct_end) f_ct -= ct_span;
-            f_dst += (uint32_t)(St::U4 * 16);
-            if (f_dst == dst_end) f_dst = dst_first;
-            --f_now;
-        }
+    // entry i of a tile, issued (the caller has tested that this wave has it)
+    auto fill_issue = [&](int i) {
+        if (i < NIMG)
+            glds16s(uniform_ptr(X + (uint64_t)f_ct * St::IMG_U4), voff + (uint32_t)(i * WAVES * 1024),
+                    f_dst + (uint32_t)(i * WAVES * 1024));
+        else glds4s(uniform_ptr(p.xns + (uint64_t)f_ct * H_BN), (uint32_t)(lane * 4), f_dst + St::IMG_U4 * 16);
     };
+    // behind a tile's last entry: on to the next tile
+    auto fill_next = [&] {
+        f_ct += ct_step;
+        if (f_ct >= ct_end) f_ct -= ct_span;
+        f_dst += (uint32_t)(St::U4 * 16);
+        if (f_dst == dst_end) f_dst = dst_first;
+    };
+    // does this wave have entry i of a tile?  (wave-uniform, fixed per launch)
+    auto has_op = [&](int i) { return i < NIMG ? wave + WAVES * i < St::IMG_U4 / 64 : wave == 0; };
     // Burst issue inside the MFMA stream: a group's OPT * TPS entries at
     // fixed places of the two halves (A, E) that follow the group barrier,
     // OPK per k-step from the first k-step on -- one wherever the halves
@@ -156,10 +157,23 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     // behind that barrier (tau_apply).  What any slot published to gtau --
     // the sorting slots' cross-slot bounds (xslot_step) -- so reaches every
     // slot within two tile groups, with no plain load that would be waited
-    // for behind the tile stream.  Issued on a group's first tile only
-    // (tj_now == 0: the tile that passed the barrier), never in the prologue:
-    // the counted wait there stays the fills' own.
+    // for behind the tile stream.  Issued on the tile that passed a group
+    // barrier only, never in the prologue: the counted wait there stays the
+    // fills' own.
+    //
+    // What the hooks of the tile being computed do is one scalar, hk: bit e
+    // is entry e's.  It is set where a burst is handed out (behind the group
+    // barrier) and is zero on every other tile, so a hook is a scalar bit
+    // test and a branch, and a tile without a burst branches past all of
+    // them.  Bit e of an entry that is not a tile's last: this wave issues
+    // that op (the burst reaches the entry's tile, and the wave has a share
+    // of the entry: has_op).  Bit e of a tile's last entry: the burst reaches
+    // that tile -- every wave then moves its fill state on (fill_next), and
+    // has_op decides the op inside, as bit 31 (fixed per wave: a scalar bit
+    // test too, not a lane mask held over the loop).  Bit OPT * TPS: the
+    // threshold refresh.
     constexpr int NENT = OPT * TPS + (XS ? 1 : 0);
+    static_assert(NENT <= 31, "a tile's hooks are the bits of one word");
     constexpr int OPK = (NENT + 2 * NS - 1) / (2 * NS);
     static_assert(NENT <= 2 * NS * OPK, "a burst fits the two halves after its barrier");
     constexpr bool DMA_IN_E = NENT > NS * OPK;   // (entries left over for phase E)
@@ -169,16 +183,32 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     typedef __attribute__((address_space(3))) unsigned int lds_u32;
     lds_u32* tau_lds = (lds_u32*)(reinterpret_cast<unsigned int*>(lds + NSTG * TPS * St::U4) + 64 * wave);
     uint32_t tau_voff = 0;   // byte offset of this lane's gtau word (per segment)
-    int tj_now = 0;          // (t + 1) % TPS of the tile being computed
+    // this wave's bits of a whole burst of TPS tiles
+    uint32_t hk_wave = 0;
+#pragma unroll
+    for (int e = 0; e < OPT * TPS; ++e)
+        if (e % OPT == OPT - 1 || has_op(e % OPT)) hk_wave |= 1u << e;
+    // the hooks of a tile that starts a burst of n tiles (0 <= n <= TPS)
+    // (readfirstlane: a scalar whatever the compiler made of its inputs)
+    auto hooks_of = [&](int n) {
+        return (uint32_t)__builtin_amdgcn_readfirstlane(
+            (hk_wave & ~(~0u << (n * OPT))) | (XS ? 1u << (OPT * TPS) : 0u) | (has_op(OPT - 1) ? 1u << 31 : 0u));
+    };
+    uint32_t hk = 0;
     auto dma_steps = [&](int half) {
         return [&, half](int k) {
 #pragma unroll
             for (int o = 0; o < OPK; ++o) {
                 const int e = (half * NS + k) * OPK + o;
                 if (e < OPT * TPS) {
-                    if (f_now > 0) fill_op(e % OPT);
+                    if (e % OPT < OPT - 1) {
+                        if (hk & (1u << e)) fill_issue(e % OPT);
+                    } else if (hk & (1u << e)) {
+                        if (hk & (1u << 31)) fill_issue(OPT - 1);
+                        fill_next();
+                    }
                 } else if (XS && e == OPT * TPS) {
-                    if (tj_now == 0) glds4s_dev<0>(p.gtau, tau_voff, tau_dst);
+                    if (hk & (1u << e)) glds4s_dev<0>(p.gtau, tau_voff, tau_dst);
                 }
             }
         };
@@ -564,15 +594,18 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         uint32_t ct = (uint32_t)p.tile_base + (uint32_t)p0 * ct_step;
         f_ct = ct;
         f_dst = dst_first;
-        f_now = ntile < 2 * TPS ? ntile : 2 * TPS;
-        f_left = ntile - f_now;
+        const int f_first = ntile < 2 * TPS ? ntile : 2 * TPS;
+        f_left = ntile - f_first;
+        hk = 0;
         // this wave's DMA ops of the newest group issued (group 1's tiles)
         const int ops_in_flight = n_ops * (ntile <= TPS ? 0 : ntile < 2 * TPS ? ntile - TPS : TPS);
 #pragma unroll
         for (int j = 0; j < 2 * TPS; ++j) {
-            if (f_now > 0) {
+            if (j < f_first) {
 #pragma unroll
-                for (int i = 0; i < OPT; ++i) fill_op(i);
+                for (int i = 0; i < OPT; ++i)
+                    if (has_op(i)) fill_issue(i);
+                fill_next();
             }
         }
         vm_wait(ops_in_flight);   // this wave's part of group 0
@@ -609,8 +642,11 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 vm_wait(0);
                 block_barrier();
 #ifndef WV_H16_ABLATE_NO_FILL
-                f_now = f_left < TPS ? f_left : TPS;
+                const int f_now = f_left < TPS ? f_left : TPS;   // tiles of this group's burst
                 f_left -= f_now;
+                hk = hooks_of(f_now);
+#else
+                hk = hooks_of(0);
 #endif
                 // the group's threshold refresh: the words the last group's
                 // DMA brought (landed: the wait above), before this group's
@@ -623,7 +659,9 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 }
             }
             tj = tj == TPS - 1 ? 0 : tj + 1;
-            tj_now = tj;
+            // (opaque from here on: the k-steps test the word's bits, not
+            // what it was made from)
+            asm volatile("" : "+s"(hk));
             // lanes l and l ^ 32 keep lists for the same query column (see the split pass)
             const bool mask_t = need_mask;
             const uint4* nimg = more ? lds + slot_t * St::U4 : img;
@@ -631,7 +669,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             // (the lane's mask words only when the tile needs them)
             if (mask_t) mask_half(acc00, acc01, lane_ok((uint32_t)okw, jq0), lane_ok((uint32_t)okw, jq1));
             float m0, m1;
-            // (a scalar test of f_now at each k-step that has an entry)
+            // (a scalar bit test of hk at each k-step that has an entry)
 #ifdef WV_H16_ABLATE_NO_MIN
             m0 = acc00[0]; m1 = acc01[0];
             mfma_half(img, 1, acc10, acc11, [](int) {}, dma_steps(0), nimg, 0);
@@ -640,7 +678,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             // (two copies of the half, so that the tiles without a burst test
             // nothing per k-step: + 20 VGPRs at the join, and scratch in the
             // XS instantiation at NS = 8)
-            if (f_now > 0) mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
+            if (hk << 1) mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
             else mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), no_dma, nimg, 0);
 #else
             mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
@@ -669,6 +707,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 if constexpr (DMA_IN_E) mfma_half(nimg, 0, acc00, acc01, min_steps(acc10, acc11, m0, m1), dma_steps(1), nimg, 1);
                 else mfma_half(nimg, 0, acc00, acc01, min_steps(acc10, acc11, m0, m1), no_dma, nimg, 1);
 #endif
+                hk = 0;   // the burst is out: the group's other tiles have no hook to run
                 need_mask = tile_ok(ct, okw);
             } else {
                 m0 = min16(acc10);

@@ -858,16 +858,12 @@ def test_h16_key_pass_seeded_equals_unseeded_and_fp32(dim, metric):
 
 
 @pytest.mark.parametrize("metric", [O.L2, O.DOT, O.COSINE])
-def test_h16_seed_list_mode(metric):
-    """The seed pre-pass in list mode (WV_H16_SEED_LISTS; a 10k-ish batch: 19 query blocks, the
-    list pass's 13 slots x 16 entries fit the seed kernel's sort): minima over
-    every 64th tile, full lists over the corpus's last 69 of 1094 tiles
-    (keys above the minima thresholds dropped), the lists' 16 smallest handed
-    to the finalize as one more slot and the main pass over the other 1025
-    tiles.  Same ids and distances as minima mode (the default), as a
-    denser minima pass (WV_H16_LIST_MULT=1) and as the fp32 pass, with
-    tombstones, a shared allow list and a partial last query block; equal to
-    the restatement up to tie order on a sample of queries."""
+def test_h16_batch_of_19_query_blocks(metric):
+    """A 10k-ish batch on the default f16 path: 9500 queries make 19 query
+    blocks of 512 (the last one partial) over the 1094 tiles of 70 001 rows,
+    with tombstones and a shared allow list.  Same ids, distances and counts
+    as the fp32 pass, equal to the restatement up to tie order on every 19th
+    query, and at most nq / 50 certificate fallbacks."""
     import os
     n, nq, dim = 70001, 9500, 128
     base, qs = _data(n, dim, nq, seed=81, metric=metric)
@@ -876,8 +872,7 @@ def test_h16_seed_list_mode(metric):
     allow_ids = np.nonzero(rng.random(n) < 0.6)[0]
     al = W.AllowList.from_ids(allow_ids, n)
     runs = []
-    for env in ({"WV_H16_SEED_LISTS": "1"}, {}, {"WV_H16_SEED_LISTS": "1", "WV_H16_LIST_MULT": "1"},
-                {"WV_BF_FP32": "1"}):
+    for env in ({}, {"WV_BF_FP32": "1"}):
         os.environ.update(env)
         try:
             ix = W.GPUVectorIndex(dim, METRIC_NAMES[metric], capacity=n)

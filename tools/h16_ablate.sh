@@ -19,7 +19,7 @@ if [ "$1" == "build" ]; then
     # the variant's defines apply to wv_h16.hip (the library's object without any)
     if [ -z "$defs" ]; then cp $C/wv_h16.o $B/h16_$name.o; else
       /opt/rocm/bin/hipcc $HF -fno-honor-nans $defs -c $C/wv_h16.hip -o $B/h16_$name.o; fi
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -pthread $B/main.o $B/h16_$name.o $C/wv_bf.o $C/wv_hnsw.o $C/wv_pq.o $C/wv_sbd.o \
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -pthread $B/main.o $B/h16_$name.o $C/wv_bf.o $C/wv_hnsw.o $C/wv_pq.o $C/wv_sbd.o $C/wv_flat_ids.o \
         $B/api.o $C/wv_batcher.o $C/wv_commitlog.o $C/wv_group.o $C/wv_mirror.o -L/opt/rocm/lib -lrccl -o $B/abl_$name
     ) &
   done

@@ -31,7 +31,6 @@ hipError_t wv_launch_bf_mfma(const wv::BfParams* p, hipStream_t s);
 hipError_t wv_launch_bf_finalize(const wv::BfFinParams* p, hipStream_t s);
 hipError_t wv_launch_bf_finalize_wide(const wv::BfFinParams* p, hipStream_t s);
 hipError_t wv_launch_exact_scan(const wv::ScanParams* p, hipStream_t s);
-hipError_t wv_launch_fb(const wv::FbParams* p, hipStream_t s);
 hipError_t wv_launch_fbd(const int32_t* flags, int nq, const wv::FbParams* fb, hipStream_t s);
 hipError_t wv_launch_fbd_mark(const int32_t* status, int nq, int32_t* flags, float* thr, const float* out_d,
                               const int32_t* out_n, int k, hipStream_t s);
@@ -266,10 +265,10 @@ struct wv_index {
     // D <= 128): f16(s_x x) in the layout of h16_index; h16_ex = max residual
     // norm |x - f16(s_x x) / s_x| over the rows (rounded up), both host-cached
     bool use_h16 = false;
-    bool h16_wide = false;  // D > 128: wv_bf_h16w_kernel (both operands through LDS, 128-row tiles)
+    bool h16_wide = false;  // D > 128: wv_bf_h16w_kernel (both operands through LDS, 256-row tiles)
     int h16_ns = 0;
     float h16_sx = 0.f, h16_ex = 0.f;
-    DevBuf ximg16, xns, qimg16, qres, qmax, qscale, tau, gtau, marg, allow_pad, ex_bits, gslot, seed_d, seed_id;
+    DevBuf ximg16, xns, qimg16, qres, qmax, qscale, tau, gtau, marg, allow_pad, ex_bits, gslot;
     // the f16 pass's block order (block_order), cached for its schedule
     DevBuf blk_order;
     std::vector<int> blk_order_host;
@@ -308,7 +307,7 @@ struct wv_index {
     DevBuf scan_d, scan_i, sort_d, sort_i, sort_tmp;
     DevBuf g_idx, g_q, g_allow, g_ids, g_d, g_n, g_cnt;
     DevBuf out_ids, out_d, out_n;
-    DevBuf fail_thr, fb_idx, fb_d, fb_i, fb_n, fb_of;
+    DevBuf fail_thr;
     DevBuf ac_cnt, ac_off, rowidx;   // allow-list compaction
     // mutable-index sync: rows added since the last graph
     // upload are "pending"; those the graph does not hold are the delta set,
@@ -527,15 +526,15 @@ static bool worth_compacting(uint64_t n_ok, uint64_t N, int nq) {
     return (double)n_ok < (double)N * f;
 }
 
-int compact_allowed(wv_index* ix, const uint64_t* d_allow, uint64_t allow_nbits, uint64_t N, uint64_t* n_ok,
-                    hipStream_t s, bool always = false, int nq = 1) {
+// The prefix both compactions share: the allowed rows counted per 64-row word
+// into ix->ac_cnt and their exclusive scan into ix->ac_off, whose entry
+// `words` = (N + 63) / 64 is then the list's length (on the device).
+static int count_allowed(wv_index* ix, const uint64_t* d_allow, uint64_t allow_words, uint64_t N, hipStream_t s) {
     const uint64_t words = (N + 63) / 64;
-    const uint64_t allow_words = (allow_nbits + 63) / 64;
     HIP_TRY(ix->ac_cnt.ensure((words + 1) * 4));
     HIP_TRY(ix->ac_off.ensure((words + 1) * 4));
-    const unsigned blocks = (unsigned)((words + 255) / 256);
-    hipLaunchKernelGGL(allowed_count_kernel, dim3(blocks), dim3(256), 0, s, d_allow, allow_words,
-                       ix->excl.as<uint64_t>(), N, ix->ac_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(allowed_count_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, d_allow,
+                       allow_words, ix->excl.as<uint64_t>(), N, ix->ac_cnt.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(ix->ac_cnt.as<uint32_t>() + words, 0, 4, s));
     size_t tmp = 0;
@@ -544,6 +543,15 @@ int compact_allowed(wv_index* ix, const uint64_t* d_allow, uint64_t allow_nbits,
     HIP_TRY(ix->sort_tmp.ensure(tmp));
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ix->sort_tmp.p, tmp, ix->ac_cnt.as<uint32_t>(), ix->ac_off.as<uint32_t>(),
                                              (int)(words + 1), s));
+    return WV_OK;
+}
+
+int compact_allowed(wv_index* ix, const uint64_t* d_allow, uint64_t allow_nbits, uint64_t N, uint64_t* n_ok,
+                    hipStream_t s, bool always = false, int nq = 1) {
+    const uint64_t words = (N + 63) / 64;
+    const uint64_t allow_words = (allow_nbits + 63) / 64;
+    const unsigned blocks = (unsigned)((words + 255) / 256);
+    if (int rc = count_allowed(ix, d_allow, allow_words, N, s)) return rc;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, ix->ac_off.as<uint32_t>() + words, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -571,19 +579,8 @@ int compact_allowed_dev(wv_index* ix, const uint64_t* d_allow, uint64_t allow_nb
                         hipStream_t s) {
     const uint64_t words = (N + 63) / 64;
     const uint64_t allow_words = (allow_nbits + 63) / 64;
-    HIP_TRY(ix->ac_cnt.ensure((words + 1) * 4));
-    HIP_TRY(ix->ac_off.ensure((words + 1) * 4));
     const unsigned blocks = (unsigned)((words + 255) / 256);
-    hipLaunchKernelGGL(allowed_count_kernel, dim3(blocks), dim3(256), 0, s, d_allow, allow_words,
-                       ix->excl.as<uint64_t>(), N, ix->ac_cnt.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(ix->ac_cnt.as<uint32_t>() + words, 0, 4, s));
-    size_t tmp = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, ix->ac_cnt.as<uint32_t>(), ix->ac_off.as<uint32_t>(),
-                                             (int)(words + 1), s));
-    HIP_TRY(ix->sort_tmp.ensure(tmp));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ix->sort_tmp.p, tmp, ix->ac_cnt.as<uint32_t>(), ix->ac_off.as<uint32_t>(),
-                                             (int)(words + 1), s));
+    if (int rc = count_allowed(ix, d_allow, allow_words, N, s)) return rc;
     const uint64_t padded = (N + wv::HW_BN - 1) / wv::HW_BN * wv::HW_BN;
     HIP_TRY(ix->rowidx.ensure(padded * 4));
     hipLaunchKernelGGL(allowed_scatter_kernel, dim3(blocks), dim3(256), 0, s, d_allow, allow_words,
@@ -606,8 +603,8 @@ int run_pq_flat(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d
 // f16 key pass (wv_h16.hip) over the whole corpus, optionally masked by a
 // shared allow list: query image + scale, an optional seed pre-pass over every
 // H_SAMPLE-th tile (its finalize yields per-query thresholds), the main pass
-// seeded with them, and the certifying finalize.  Appends uncertified queries
-// to `fails` (read back from the device).
+// seeded with them, and the certifying finalize, which flags uncertified
+// queries in ix->fail for the device-resolved fallback (queue_fbd).
 // rowidx (nullable): the ascending row list of a compacted shared allow list
 // (compact_allowed) -- the pass then runs over an f16 image of just those N
 // rows (gathered here) and the candidate ids are mapped back to rows before
@@ -647,17 +644,15 @@ int block_order(wv_index* ix, uint64_t nqb, const wv::BfSchedule& sch, hipStream
 }
 
 int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_allow, uint64_t allow_nbits, uint64_t N,
-            uint64_t* d_out_ids, float* d_out_d, int32_t* d_out_n, hipStream_t s, std::vector<int32_t>& fails,
+            uint64_t* d_out_ids, float* d_out_d, int32_t* d_out_n, hipStream_t s,
             const uint32_t* rowidx = nullptr, const uint32_t* n_dev = nullptr) {
     const int ns = ix->h16_ns;
     const bool wd = ix->h16_wide;   // D > 128: the wide-D kernel
     // D <= 128: 8-wave (512-query) workgroups, one per CU; D > 128: 256-row
     // tiles x 256-query blocks, one workgroup per CU
-    const int wg_per_cu = 1;
     const int tile_rows = wd ? wv::HW_BN : wv::H_BN, bq = wd ? wv::HW_BQ : 512;
-    // seed minima per query and slot; lists per query and slot, entries per list
-    const int seed_prod = wd ? wv::HW_PROD : wv::H_PROD;
-    const int prod = seed_prod;
+    // lists (and seed minima) per query and slot, entries per list
+    const int prod = wd ? wv::HW_PROD : wv::H_PROD;
     const int kp = wv::BF_KP;
     const uint64_t ntl = (N + tile_rows - 1) / tile_rows;
     const uint64_t words = ntl * (uint64_t)(tile_rows / 64);   // allow words the kernel reads
@@ -721,13 +716,10 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     hp.xns = ix->xns.as<float>();
     hp.excl = excl;
     hp.allow = allow;
-    hp.qscale = ix->qscale.as<float>();
-    hp.sx = ix->h16_sx;
     hp.N = N;
     hp.nq = nq;
     hp.metric = ix->metric;
     hp.n_qblocks = nqb;
-    hp.wide_rows = 128;
     // 64-row tiles the pass need not mask: every row present and eligible
     // (no allow list; a compacted scan: the rows below N)
     hp.clean_tiles = wd ? 0 : rowidx ? N / wv::H_BN : allow ? 0 : std::min<uint64_t>(ix->clean_words, N / wv::H_BN);
@@ -766,7 +758,7 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     // and fail the certificate); the seed pass needs >= k minima likewise
     const bool wide = k > wv::FIN_KF;
     auto target = [&](uint64_t tiles) {
-        uint64_t t = (uint64_t)ix->n_cus * wg_per_cu;
+        uint64_t t = (uint64_t)ix->n_cus;
         if (wide) t = std::max<uint64_t>(t, (uint64_t)nqb * std::min<uint64_t>(tiles, (uint64_t)k + 2));
         return (int)std::min<uint64_t>(t, 1u << 30);
     };
@@ -779,28 +771,12 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     // main pass will run the cross-slot exchange, its bounds overtake the
     // seed's within the first eighth of a segment, so a sparser seed costs
     // fewer insertion events than its pre-pass saves (H_SAMPLE_XS; the main
-    // pass's schedule does not depend on the stride outside list mode).
+    // pass's schedule does not depend on the stride).
     int sample = wv::H_SAMPLE;
-    if (!wd && !n_dev && !std::getenv("WV_H16_SEED_LISTS") &&
-        xs_fits(wv::bf_schedule(nq, N, target(ntl), bq, tile_rows)))
-        sample = wv::H_SAMPLE_XS;
+    if (!wd && !n_dev && xs_fits(wv::bf_schedule(nq, N, target(ntl), bq, tile_rows))) sample = wv::H_SAMPLE_XS;
     if (const char* e = std::getenv("WV_H16_SAMPLE")) sample = std::max(1, std::atoi(e));
     // (seeded from H_SEED_MIN_TILES tiles on, whatever the stride)
     const bool seed = !wd && ntl >= (uint64_t)wv::H_SEED_MIN_TILES && !std::getenv("WV_H16_NO_SEED");
-    // The seed pre-pass over 1 / sample of the tiles.  List mode
-    // (WV_H16_SEED_LISTS, where its lists fit the seed kernel's one-wave
-    // sort; measured slower, profiles/r06/h16_seed_list_mode.log): the
-    // pre-pass scans the corpus's last nts tiles with full lists, the seed
-    // kernel takes the thresholds from them and hands their 2 BF_KP smallest
-    // to the finalize as one more slot, and the main pass scans only the
-    // other tiles -- no tile is scanned twice.  Otherwise (minima mode) it
-    // scans every sample-th tile keeping minima, and the main pass all tiles.
-    const uint64_t nts = seed ? (ntl + sample - 1) / sample : 0;
-    wv::BfSchedule ss{};
-    if (seed) ss = wv::bf_schedule(nq, nts * wv::H_BN, target(nts), bq, wv::H_BN);
-    const bool seed_lists = seed && !wide && !n_dev && k <= 64 &&
-                            (uint64_t)ss.n_slots * wv::H_PROD * wv::BF_KP <= 256 && std::getenv("WV_H16_SEED_LISTS");
-    const uint64_t ntl_main = seed_lists ? ntl - nts : ntl;
     // the wide pass: query blocks cut at the same tile offsets where that
     // costs no work (bf_schedule_aligned)
     wv::BfSchedule sch{};
@@ -818,25 +794,21 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     }
     if (wd && !wide && sch.n_blocks == 0) sch = wv::bf_schedule_aligned(nq, N, target(ntl), bq, tile_rows, false);
     if (sch.n_blocks == 0)
-        sch = wv::bf_schedule(nq, seed_lists ? ntl_main * tile_rows : N, target(ntl_main), bq, tile_rows);
+        sch = wv::bf_schedule(nq, N, target(ntl), bq, tile_rows);
     if (wide && (uint64_t)sch.n_slots * prod * kp > (uint64_t)wv::FINW_NE)
         return fail(WV_ESTATE, "run_h16: too many lists for the wide finalize");
-    // list slots per query: the main pass's, + the seed's slot (list mode)
-    const int out_slots = sch.n_slots + (seed_lists ? 1 : 0);
-    HIP_TRY(ix->cand_d.ensure((size_t)nq * out_slots * prod * kp * 4));
-    HIP_TRY(ix->cand_id.ensure((size_t)nq * out_slots * prod * kp * 4));
-    // a seed pre-pass: minima over every stride-th tile -> thresholds (tau)
-    auto seed_minima = [&](int stride) -> int {
-        const uint64_t nt = (ntl + stride - 1) / stride;
+    HIP_TRY(ix->cand_d.ensure((size_t)nq * sch.n_slots * prod * kp * 4));
+    HIP_TRY(ix->cand_id.ensure((size_t)nq * sch.n_slots * prod * kp * 4));
+    // the seed pre-pass: minima over every sample-th tile -> thresholds (tau, gtau)
+    auto seed_minima = [&]() -> int {
+        const uint64_t nt = (ntl + sample - 1) / sample;
         const wv::BfSchedule ms = wv::bf_schedule(nq, nt * wv::H_BN, target(nt), bq, wv::H_BN);
-        HIP_TRY(ix->cand_d.ensure((size_t)nq * std::max(ms.n_slots * seed_prod, out_slots * prod * kp) * 4));
+        HIP_TRY(ix->cand_d.ensure((size_t)nq * std::max(ms.n_slots * prod, sch.n_slots * prod * kp) * 4));
         hp.ntiles = ms.ntiles;
         hp.ntiles_real = ms.ntiles;
         hp.units_per_block = ms.units_per_block;
         hp.n_slots = ms.n_slots;
-        hp.tile_stride = stride;
-        hp.tile_base = 0;
-        hp.tau = nullptr;
+        hp.tile_stride = sample;
         hp.out_d = ix->cand_d.as<float>();
         hp.out_id = nullptr;
         HIP_TRY(wv_launch_bf_h16(&hp, ns, 1, s));
@@ -858,59 +830,20 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
         sp.tau = ix->tau.as<float>();
         sp.gtau = ix->gtau.as<unsigned int>();
         sp.bq = bq;
-        sp.prod = seed_prod;
-        if (seed_lists) {
-            // list mode: the list pass over the corpus's last nts tiles,
-            // keys above the minima's thresholds dropped; its lists give
-            // tighter thresholds (min with the minima's) and the finalize's
-            // extra slot
-            HIP_TRY(wv_launch_h16_seed(&sp, s));
-            HIP_TRY(ix->seed_d.ensure((size_t)nq * ss.n_slots * prod * kp * 4));
-            HIP_TRY(ix->seed_id.ensure((size_t)nq * ss.n_slots * prod * kp * 4));
-            hp.ntiles = ss.ntiles;
-            hp.ntiles_real = ss.ntiles;
-            hp.units_per_block = ss.units_per_block;
-            hp.n_slots = ss.n_slots;
-            hp.tile_stride = 1;
-            hp.tile_base = ntl_main;
-            hp.tau = ix->tau.as<float>();
-            hp.out_d = ix->seed_d.as<float>();
-            hp.out_id = ix->seed_id.as<uint32_t>();
-            HIP_TRY(wv_launch_bf_h16(&hp, ns, 0, s));
-            hp.tile_base = 0;
-            hp.tau = nullptr;
-            sp.minima = ix->seed_d.as<float>();
-            sp.ids = ix->seed_id.as<uint32_t>();
-            sp.n_slots = ss.n_slots;
-            sp.ntiles = ss.ntiles;
-            sp.units_per_block = ss.units_per_block;
-            sp.prod = prod * kp;
-            sp.out_d = ix->cand_d.as<float>();
-            sp.out_id = ix->cand_id.as<uint32_t>();
-            sp.out_slots = out_slots;
-            sp.out_ntiles = sch.ntiles;
-            sp.out_upb = sch.units_per_block;
-        }
         HIP_TRY(wv_launch_h16_seed(&sp, s));
         return WV_OK;
     };
     if (seed) {
         TREC(6);
-        // (list mode: minima over every 4 sample-th tile for the list pass;
-        // WV_H16_LIST_MULT: that factor, for measurements)
-        int mult = 4;
-        if (const char* e = std::getenv("WV_H16_LIST_MULT")) mult = std::max(1, std::atoi(e));
-        if (int rc = seed_minima(seed_lists ? mult * sample : sample)) return rc;
+        if (int rc = seed_minima()) return rc;
         TREC(7);
     }
     hp.ntiles = sch.ntiles;
-    hp.ntiles_real = ntl_main;
-    hp.out_slots = seed_lists ? out_slots : 0;
+    hp.ntiles_real = ntl;
     hp.units_per_block = sch.units_per_block;
     hp.n_slots = sch.n_slots;
     hp.n_dev = n_dev;
     hp.tile_stride = 1;
-    hp.tau = nullptr;
     // the running threshold (k <= 2 BF_KP), started at the seed's
     if (!seed) HIP_TRY(hipMemsetAsync(ix->gtau.p, 0xFF, (size_t)nq * 4, s));
     hp.gtau = ix->gtau.as<unsigned int>();
@@ -942,7 +875,7 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     // the 8-wave D <= 128 pass on the flat schedule: tiles rotated per query
     // block (locality bit 2): 2.73-2.75 -> 2.66-2.68 ms per 1M x 10k pass,
     // L2-miss bytes 5.23 -> 0.66 GB
-    const bool rotate = !wd && nqb >= 2 && sch.ntiles == ntl_main;
+    const bool rotate = !wd && nqb >= 2 && sch.ntiles == ntl;
     if (rotate) hp.locality |= 2;
     if (int rc = block_order(ix, (uint64_t)nqb, sch, s, &hp.block_order, rotate)) return rc;
     TREC(0);
@@ -961,8 +894,7 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     }
     fp.cand_d = ix->cand_d.as<float>();
     fp.cand_id = ix->cand_id.as<uint32_t>();
-    fp.n_slots = out_slots;
-    fp.extra_slot = seed_lists ? 1 : 0;
+    fp.n_slots = sch.n_slots;
     fp.ntiles = sch.ntiles;
     fp.units_per_block = sch.units_per_block;
     HIP_TRY(wv_launch_h16_gtau(ix->gtau.as<unsigned int>(), nq, ix->h16_sx, ix->qscale.as<float>(), ix->tau.as<float>(),
@@ -971,7 +903,6 @@ int run_h16(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_all
     TREC(2);
     HIP_TRY(wide ? wv_launch_bf_finalize_wide(&fp, s) : wv_launch_bf_finalize(&fp, s));
     TREC(3);
-    (void)fails;   // uncertified queries are resolved on the device (queue_fbd)
     return WV_OK;
 }
 
@@ -1035,7 +966,6 @@ int run_exact(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_a
         if (nq) HIP_TRY(hipMemsetAsync(d_out_n, 0, sizeof(int32_t) * nq, s));
         return WV_OK;
     }
-    std::vector<int32_t> fails;
     // the f16 pass (whole corpus or a shared allow list) serves k up to
     // BF_WIDE_KMAX; the other key passes k up to BF_FAST_KMAX
     const bool h16_ok = ix->use_h16 && !allow_stride && !d_rowmask;
@@ -1063,8 +993,7 @@ int run_exact(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_a
                 return WV_OK;
             }
             if (int rc = compact_allowed_dev(ix, cmask, cbits, N, &n_dev, s)) return rc;
-            std::vector<int32_t> none;
-            if (int rc = run_h16(ix, d_q, nq, k, nullptr, 0, n_bound, d_out_ids, d_out_d, d_out_n, s, none,
+            if (int rc = run_h16(ix, d_q, nq, k, nullptr, 0, n_bound, d_out_ids, d_out_d, d_out_n, s,
                                  ix->rowidx.as<uint32_t>(), n_dev))
                 return rc;
             return queue_fbd(ix, d_q, nq, k, d_allow, allow_nbits, allow_stride, d_out_ids, d_out_d, d_out_n, s);
@@ -1082,8 +1011,7 @@ int run_exact(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_a
             // else (below 1/2 or 1/8) on the fp32 pass over the row list
             const bool compact = (worth_compacting(n_ok, N, nq) && !std::getenv("WV_BF_NO_COMPACT")) || d_rowmask;
             if (compact && h16_ok) {
-                std::vector<int32_t> none;
-                int rc2 = run_h16(ix, d_q, nq, k, nullptr, 0, n_ok, d_out_ids, d_out_d, d_out_n, s, none,
+                int rc2 = run_h16(ix, d_q, nq, k, nullptr, 0, n_ok, d_out_ids, d_out_d, d_out_n, s,
                                   ix->rowidx.as<uint32_t>());
                 if (rc2) return rc2;
                 return queue_fbd(ix, d_q, nq, k, d_allow, allow_nbits, allow_stride, d_out_ids, d_out_d, d_out_n, s);
@@ -1098,7 +1026,7 @@ int run_exact(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_a
         }
         if (ix->use_h16 && !d_rowidx && !allow_stride) {
             const uint64_t* sh = d_allow && !allow_stride ? d_allow : nullptr;
-            int rc = run_h16(ix, d_q, nq, k, sh, allow_nbits, N, d_out_ids, d_out_d, d_out_n, s, fails);
+            int rc = run_h16(ix, d_q, nq, k, sh, allow_nbits, N, d_out_ids, d_out_d, d_out_n, s);
             if (rc) return rc;
             return queue_fbd(ix, d_q, nq, k, d_allow, allow_nbits, allow_stride, d_out_ids, d_out_d, d_out_n, s);
         }
@@ -1193,60 +1121,10 @@ int run_exact(wv_index* ix, const float* d_q, int nq, int k, const uint64_t* d_a
         HIP_TRY(wv_launch_bf_finalize(&fp, s));
         TREC(3);
         return queue_fbd(ix, d_q, nq, k, d_allow, allow_nbits, allow_stride, d_out_ids, d_out_d, d_out_n, s);
-    } else {
-        for (int i = 0; i < nq; ++i) fails.push_back(i);
     }
-    ix->last_fallbacks += fails.size();
-#ifdef WV_ABLATION_BUILD
-    if (!fails.empty() && std::getenv("WV_ABLATE_NO_FALLBACK")) fails.clear();   // kernel ablations only
-#endif
-    if (!fails.empty() && keyed) {
-        // batched threshold filter over the corpus for every failed query
-        std::vector<int32_t> rest;
-        for (size_t b0 = 0; b0 < fails.size(); b0 += 256) {
-            const int nf = (int)std::min<size_t>(256, fails.size() - b0);
-            HIP_TRY(ix->fb_idx.ensure((size_t)nf * 4));
-            HIP_TRY(ix->fb_d.ensure((size_t)nf * wv::FB_CAP * 4));
-            HIP_TRY(ix->fb_i.ensure((size_t)nf * wv::FB_CAP * 4));
-            HIP_TRY(ix->fb_n.ensure((size_t)nf * 4));
-            HIP_TRY(ix->fb_of.ensure((size_t)nf * 4));
-            HIP_TRY(hipMemcpyAsync(ix->fb_idx.p, fails.data() + b0, 4 * (size_t)nf, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemsetAsync(ix->fb_n.p, 0, 4 * (size_t)nf, s));
-            wv::FbParams bp{};
-            bp.X = ix->vecs.as<float>();
-            bp.Q = d_q;
-            bp.qidx = ix->fb_idx.as<int32_t>();
-            bp.thr = ix->fail_thr.as<float>();
-            bp.tomb = ix->excl.as<uint64_t>();
-            bp.tomb_nbits = ix->capacity;
-            bp.allow = d_allow;
-            bp.allow_nbits = allow_nbits;
-            bp.allow_stride = allow_stride;
-            bp.N = N;
-            bp.nf = nf;
-            bp.D = ix->dim;
-            bp.ldx = ix->ldx;
-            bp.ldq = ix->dpad;
-            bp.metric = ix->metric;
-            bp.k = k;
-            bp.id_base = ix->cfg.id_base;
-            bp.cand_d = ix->fb_d.as<float>();
-            bp.cand_id = ix->fb_i.as<uint32_t>();
-            bp.cand_n = ix->fb_n.as<uint32_t>();
-            bp.out_ids = d_out_ids;
-            bp.out_d = d_out_d;
-            bp.out_n = d_out_n;
-            bp.overflow = ix->fb_of.as<int32_t>();
-            HIP_TRY(wv_launch_fb(&bp, s));
-            std::vector<int32_t> of(nf);
-            HIP_TRY(hipMemcpyAsync(of.data(), ix->fb_of.p, 4 * (size_t)nf, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            for (int i = 0; i < nf; ++i)
-                if (of[i]) rest.push_back(fails[b0 + i]);
-        }
-        fails.swap(rest);   // survivors overflowed: full scan + sort below
-    }
-    for (int q : fails) {
+    // k past every key pass: each query by a full scan and sort
+    ix->last_fallbacks += (uint64_t)nq;
+    for (int q = 0; q < nq; ++q) {
         const uint64_t* al = d_allow ? d_allow + (allow_stride ? (uint64_t)q * allow_stride : 0) : nullptr;
         int rc = ix->pq_on ? run_pq_flat(ix, d_q + (size_t)q * ix->dpad, 1, k, al, allow_nbits, 0,
                                          d_out_ids + (size_t)q * k, d_out_d + (size_t)q * k, d_out_n + q, s, nullptr, 0)
@@ -1874,7 +1752,7 @@ int wv_index_destroy(wv_index* ix) {
                       &ix->tomb, &ix->excl, &ix->q_in, &ix->q_norm, &ix->q_nrm2, &ix->q_scaled, &ix->cand_d, &ix->cand_id,
                       &ix->fail, &ix->status, &ix->counters, &ix->scan_d, &ix->scan_i, &ix->sort_d, &ix->sort_i,
                       &ix->sort_tmp, &ix->g_idx, &ix->g_q, &ix->g_allow, &ix->g_ids, &ix->g_d, &ix->g_n, &ix->g_cnt,
-                      &ix->out_ids, &ix->out_d, &ix->out_n, &ix->stage, &ix->fail_thr, &ix->fb_idx, &ix->fb_d, &ix->fb_i, &ix->fb_n, &ix->fb_of,
+                      &ix->out_ids, &ix->out_d, &ix->out_n, &ix->stage, &ix->fail_thr,
                       &ix->ac_cnt, &ix->ac_off, &ix->rowidx, &ix->pq_cent, &ix->pq_codes, &ix->pk_key,
                       &ix->pk_dist, &ix->pk_val, &ix->pk_skey, &ix->pk_sval, &ix->pk_off, &ix->ximg16, &ix->qmax_part, &ix->xns,
                       &ix->qimg16, &ix->qres, &ix->qmax, &ix->qscale, &ix->tau, &ix->gtau, &ix->marg, &ix->allow_pad, &ix->ex_bits, &ix->gslot, &ix->blk_order,

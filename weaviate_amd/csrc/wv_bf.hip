@@ -640,7 +640,7 @@ template <int METRIC, bool FAST>
 __device__ __forceinline__ void finalize_one(const BfFinParams& p, int q, float* sd, uint32_t* si, float* qv,
                                              float* kept_d, uint32_t* kept_i) {
     const int lane = threadIdx.x & 63;
-    const int n_lists = (bf_slots_of((uint64_t)(q / p.bq), p.ntiles, p.units_per_block) + p.extra_slot) * p.prod;
+    const int n_lists = bf_slots_of((uint64_t)(q / p.bq), p.ntiles, p.units_per_block) * p.prod;
     const int kp = p.kp ? p.kp : BF_KP;   // entries per list
     const int n_ent = n_lists * kp;
     const float* cd = p.cand_d + (size_t)q * p.n_slots * p.prod * kp;
@@ -1114,87 +1114,6 @@ __global__ __launch_bounds__(256) void wv_exact_scan_kernel(ScanParams p) {
 }
 
 // ---------------------------------------------------------------------------
-// Certificate fallback, batched over failed queries (see FbParams).
-template <int METRIC>
-__device__ void fb_filter(const FbParams& p, const float* qv, int f) {
-    const int g = threadIdx.x & 7;
-    const uint64_t grp = (uint64_t)blockIdx.x * (blockDim.x >> 3) + (threadIdx.x >> 3);
-    const uint64_t stride = (uint64_t)gridDim.x * (blockDim.x >> 3);
-    const int q = p.qidx[f];
-    const float thr = p.thr[q];
-    const uint64_t* al = p.allow ? p.allow + (p.allow_stride ? (uint64_t)q * p.allow_stride : 0) : nullptr;
-    for (uint64_t r = grp; r < p.N; r += stride) {
-        const float d = exact_dist_group8<METRIC>(qv, p.X + r * p.ldx, p.D, g);
-        if (g == 0 && d <= thr) {
-            bool ok = true;
-            if (p.tomb) ok = !bit_test(p.tomb, p.tomb_nbits, r);
-            if (al && ok) ok = bit_test(al, p.allow_nbits, r);
-            if (ok) {
-                const uint32_t pos = atomicAdd(&p.cand_n[f], 1u);
-                if (pos < FB_CAP) {
-                    p.cand_d[(size_t)f * FB_CAP + pos] = d;
-                    p.cand_id[(size_t)f * FB_CAP + pos] = (uint32_t)r;
-                }
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void wv_fb_filter_kernel(FbParams p) {
-    extern __shared__ float qv[];
-    const int f = blockIdx.y;
-    const int dpad = (p.D + 3) & ~3;
-    for (int i = threadIdx.x; i < dpad; i += blockDim.x)
-        qv[i] = i < p.D ? p.Q[(size_t)p.qidx[f] * p.ldq + i] : 0.f;
-    __syncthreads();
-    if (p.metric == WV_METRIC_L2) fb_filter<WV_METRIC_L2>(p, qv, f);
-    else if (p.metric == WV_METRIC_DOT) fb_filter<WV_METRIC_DOT>(p, qv, f);
-    else fb_filter<WV_METRIC_COSINE>(p, qv, f);
-}
-
-// one workgroup per failed query: bitonic sort of the survivors by (d, id)
-__global__ __launch_bounds__(1024) void wv_fb_select_kernel(FbParams p) {
-    __shared__ float sd[FB_CAP];
-    __shared__ uint32_t si[FB_CAP];
-    const int f = blockIdx.x;
-    const uint32_t n_all = p.cand_n[f];
-    const int n = (int)(n_all < (uint32_t)FB_CAP ? n_all : (uint32_t)FB_CAP);
-    int len = 1;
-    while (len < n) len <<= 1;
-    for (int i = threadIdx.x; i < len; i += blockDim.x) {
-        sd[i] = i < n ? p.cand_d[(size_t)f * FB_CAP + i] : __builtin_inff();
-        si[i] = i < n ? p.cand_id[(size_t)f * FB_CAP + i] : WV_NIL;
-    }
-    __syncthreads();
-    for (int kk = 2; kk <= len; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < len; i += blockDim.x) {
-                const int o = i ^ j;
-                if (o > i) {
-                    const bool asc = (i & kk) == 0;
-                    const bool gt = key_less(sd[o], si[o], sd[i], si[i]);
-                    if (gt == asc) {
-                        const float td = sd[i]; sd[i] = sd[o]; sd[o] = td;
-                        const uint32_t ti = si[i]; si[i] = si[o]; si[o] = ti;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const int q = p.qidx[f];
-    const int m = n < p.k ? n : p.k;
-    for (int i = threadIdx.x; i < m; i += blockDim.x) {
-        p.out_ids[(size_t)q * p.k + i] = p.id_base + si[i];
-        p.out_d[(size_t)q * p.k + i] = sd[i];
-    }
-    if (threadIdx.x == 0) {
-        p.out_n[q] = m;
-        p.overflow[f] = n_all > (uint32_t)FB_CAP ? 1 : 0;
-    }
-}
-
-// ---------------------------------------------------------------------------
 // Device-resolved certificate fallback (wv_api.hip queues it after every keyed
 // pass and after the HNSW kernel, so a batch needs no host round trip):
 //  1. compact: the failed queries (flag != 0) listed in query order, count;
@@ -1648,20 +1567,6 @@ hipError_t wv_launch_bf_finalize_wide(const wv::BfFinParams* p, hipStream_t s) {
     p = &pp;
     const size_t lds = (((p->D + 3) & ~3) + 2 * (size_t)ne + 9) * sizeof(float);
     hipLaunchKernelGGL(wv::wv_bf_finalize_wide_kernel, dim3(p->nq), dim3(256), lds, s, *p);
-    return hipGetLastError();
-}
-
-hipError_t wv_launch_fb(const wv::FbParams* p, hipStream_t s) {
-    if (p->nf == 0) return hipSuccess;
-    uint64_t blocks = (p->N + 255) / 256;
-    const uint64_t cap = (uint64_t)(2048 / (p->nf > 0 ? p->nf : 1)) + 64;
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) blocks = 1;
-    const size_t lds = ((p->D + 3) & ~3) * sizeof(float);
-    hipLaunchKernelGGL(wv::wv_fb_filter_kernel, dim3((unsigned)blocks, p->nf), dim3(256), lds, s, *p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wv::wv_fb_select_kernel, dim3(p->nf), dim3(1024), 0, s, *p);
     return hipGetLastError();
 }
 

@@ -76,8 +76,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     const uint4* __restrict__ X = reinterpret_cast<const uint4*>(p.X);
     const uint4* __restrict__ Qg = reinterpret_cast<const uint4*>(p.Q);
     const bool has_allow = p.allow != nullptr;
-    // key scale s = s_x * s_q: the seed thresholds arrive in true units
-    const float s = p.sx * p.qscale[0];
     int lb = (int)blockIdx.x;
     if ((p.locality & 1) && gridDim.x >= 8) {   // bijective XCD remap (blocks b, b + 8, ... share an XCD)
         const int nwg = (int)gridDim.x, q8 = nwg / 8, r8 = nwg % 8, xcd = (int)blockIdx.x % 8;
@@ -89,11 +87,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     if (u_last > (uint64_t)p.n_qblocks * p.ntiles) u_last = (uint64_t)p.n_qblocks * p.ntiles;
 
     const uint32_t lds0 = lds_addr(lds);
-#ifdef WV_H16_PRIO
-    // the second-dispatched half of the workgroup loses every issue
-    // arbitration to its SIMD partner: static priority for it (guide T5)
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     // this wave's LDS-DMA ops per tile (the counted waits below)
     const int n_ops = (wave < St::IMG_U4 / 64 ? (St::IMG_U4 / 64 - 1 - wave) / WAVES + 1 : 0) +
                       ((wave == 0 && L2) ? 1 : 0);
@@ -123,7 +116,11 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
     constexpr int OPT = NIMG + (L2 ? 1 : 0);
     // corpus tile index of a scanned tile: 32-bit, + ct_step per tile, - ct_span past ct_end
     const uint32_t ct_step = (uint32_t)p.tile_stride, ct_span = (uint32_t)(p.ntiles * (uint64_t)p.tile_stride);
-    const uint32_t ct_end = (uint32_t)p.tile_base + ct_span;
+    // (ct_end = ct_span, kept a scalar of its own: compared with ct_span itself
+    // the wrap becomes s_sub + s_min_u32, a shorter listing that measured
+    // about 1 % slower per 1M x 10k key pass, profiles/h16_retire/)
+    uint32_t ct_end = ct_span;
+    asm volatile("" : "+s"(ct_end));
     const uint32_t dst_first = lds0 + (uint32_t)(wave * 1024), dst_end = dst_first + (uint32_t)(NSTG * TPS * St::U4 * 16);
     uint32_t f_ct = 0, f_dst = dst_first;
     int f_left = 0;   // tiles of the segment not handed to a burst yet
@@ -257,9 +254,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         if (!SEED && p.gtau) {
             if (jq0 < p.nq) tau0 = fminf(FLT_MAX, h16_key_dec(p.gtau[jq0]));
             if (jq1 < p.nq) tau1 = fminf(FLT_MAX, h16_key_dec(p.gtau[jq1]));
-        } else if (p.tau) {
-            if (jq0 < p.nq) tau0 = fminf(FLT_MAX, p.tau[jq0] * s);
-            if (jq1 < p.nq) tau1 = fminf(FLT_MAX, p.tau[jq1] * s);
         }
         // the padding columns of a partial query block never extract (every
         // later threshold update is a min): their tiles need no row mask
@@ -340,11 +334,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef WV_H16_ABLATE_NO_LDS
-                if (k + 2 < NS) { a[(k + 2) % 3] = bq1[k + 2]; a[(k + 2) % 3].x ^= (uint32_t)rb; }
-#else
                 if (k + 2 < NS) a[(k + 2) % 3] = img[(rb * NS + k + 2) * 64 + lane];
-#endif
                 // (unconditional: a branch here would make every later wait
                 // drain these reads too; with one k-step at k = 0, after the
                 // copies above)
@@ -354,7 +344,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                                                               0, 0, 0);
                 accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(ak, __builtin_bit_cast(half8, bq1[k]), k == 0 ? xc : accB,
                                                               0, 0, 0);
-#ifndef WV_H16_XC_INPLACE
                 // (xc stays live past both first MFMAs: neither accumulator
                 // is allocated in place of the C-in, whose registers the next
                 // half's head then reuses -- in place, the head landed on a
@@ -362,7 +351,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
                 // v_mov_b64 + s_nop per half, and the loop-carried C-in once
                 // more per tile)
                 if (k == 0) asm volatile("" ::"v"(xc));
-#endif
                 dma(k);
                 between(k);
             }
@@ -565,14 +553,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             if (m0 == 1234.5f) l0d[0] = m1 + pt0 + pt1;
             return false;
 #endif
-#ifdef WV_H16_ABLATE_NO_EVENTS
-            // (ablation: the extraction code stays, no event ever fires)
-            float nev = -INF;
-            asm volatile("" : "+v"(nev));
-            const bool x0 = m0 <= fminf(fminf(l0d[BF_KP - 1], pt0), nev), x1 = m1 <= fminf(fminf(l1d[BF_KP - 1], pt1), nev);
-#else
             const bool x0 = m0 <= fminf(l0d[BF_KP - 1], pt0), x1 = m1 <= fminf(l1d[BF_KP - 1], pt1);
-#endif
             const bool any = __any(x0 || x1);
             if (__builtin_expect(any, 0)) {
                 WV_DBG_COUNT(3)
@@ -591,7 +572,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         // The first two groups at once: nothing to compute beside them yet.
         const uint64_t p0 = phys(t_begin);   // the first scanned tile (rotated)
         // corpus tile of tile t (the first: the fill starts there too)
-        uint32_t ct = (uint32_t)p.tile_base + (uint32_t)p0 * ct_step;
+        uint32_t ct = (uint32_t)p0 * ct_step;
         f_ct = ct;
         f_dst = dst_first;
         const int f_first = ntile < 2 * TPS ? ntile : 2 * TPS;
@@ -674,15 +655,10 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             m0 = acc00[0]; m1 = acc01[0];
             mfma_half(img, 1, acc10, acc11, [](int) {}, dma_steps(0), nimg, 0);
 #else
-#ifdef WV_H16_FILL_DUP
-            // (two copies of the half, so that the tiles without a burst test
-            // nothing per k-step: + 20 VGPRs at the join, and scratch in the
-            // XS instantiation at NS = 8)
-            if (hk << 1) mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
-            else mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), no_dma, nimg, 0);
-#else
+            // (two copies of the half, one without hooks, so that the tiles
+            // without a burst tested nothing per k-step, cost + 20 VGPRs at
+            // the join, and scratch in the XS instantiation at NS = 8)
             mfma_half(img, 1, acc10, acc11, min_steps(acc00, acc01, m0, m1), dma_steps(0), nimg, 0);
-#endif
 #endif
             // ---- B ----
             bool grew = false;   // a list of this wave changed: thresholds to refresh
@@ -742,7 +718,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             if (jq1 < p.nq) p.out_d[((size_t)jq1 * p.n_slots + slot) * H_PROD + khalf] = l1d[0];
             continue;
         }
-        const size_t per_q = (size_t)(p.out_slots ? p.out_slots : p.n_slots) * H_PROD * BF_KP;
+        const size_t per_q = (size_t)p.n_slots * H_PROD * BF_KP;
         if (jq0 < p.nq) {
             const size_t base = (size_t)jq0 * per_q + ((size_t)slot * H_PROD + khalf) * BF_KP;
 #pragma unroll
@@ -760,10 +736,10 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
 // f16 key pass for D > 128 (C4's 768-d dot product): both operands through
 // LDS.  Workgroup = 512 threads, one per CU; tile = 2 WR corpus rows x 256
 // queries; wave w computes rows WR (w & 1) .. +WR x queries 64 (w >> 1) .. +64
-// (WR / 32 x 2 accumulators of 32 x 32).  WR = 128 (the default): 256 x 256
-// tiles, 2-step chunks -- per MFMA half the query-side bytes and LDS-DMA ops
-// of WR = 64 (128 x 256 tiles, 4-step chunks; 48 KiB per chunk and CU for 16
-// MFMAs a wave, which left the loop waiting on the DMA: ablation, DESIGN
+// (WR / 32 x 2 accumulators of 32 x 32).  WR = 128: 256 x 256 tiles, 2-step
+// chunks -- per MFMA half the query-side bytes and LDS-DMA ops of the retired
+// WR = 64 tile (128 x 256 tiles, 4-step chunks; 48 KiB per chunk and CU for
+// 16 MFMAs a wave, which left the loop waiting on the DMA: ablation, DESIGN
 // §3.2).  The corpus and query images are h16_index images with ns 16-k steps
 // (ns a multiple of HW_KC, zero padded), so a chunk (KC steps) of a 32-row
 // group is KC contiguous 1 KiB operand blocks: LDS-DMA'd as is, read back as
@@ -772,11 +748,11 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
 // holds s|x|^2 (the L2 C-in) and the tile's exclusion / allow words.  The
 // epilogue -- mask, minima, candidate extraction into the same per-lane lists
 // as the D <= 128 pass -- runs once per tile, i.e. once per ns / KC chunks.
-template <int WR>
 struct HWStage {
+    static constexpr int WR = 128;                  // corpus rows per wave
     static constexpr int RG = WR / 32;              // row groups per wave
     static constexpr int BN = 2 * WR;               // corpus rows per tile
-    static constexpr int KC = WR == 64 ? HW_KC : HW_KC / 2;   // 16-k steps per chunk
+    static constexpr int KC = HW_KC / 2;            // 16-k steps per chunk
     static constexpr int A_U4 = 2 * RG * KC * 64;   // the tile's row groups x KC steps x 64 lanes (16 KiB)
     static constexpr int B_U4 = 8 * KC * 64;        // 8 query groups
     static constexpr int U4 = A_U4 + B_U4;
@@ -786,11 +762,11 @@ struct HWStage {
 };
 constexpr int HW_STAGES = 3;
 
-template <bool L2, int WR>
+template <bool L2>
 __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
     extern __shared__ uint4 lds[];
-    using St = HWStage<WR>;
-    constexpr int RG = St::RG, KC = St::KC, BN = St::BN;
+    using St = HWStage;
+    constexpr int WR = St::WR, RG = St::RG, KC = St::KC, BN = St::BN;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -889,18 +865,14 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
             // (wave-uniform by construction; readfirstlane tells the compiler,
             // which must keep the LDS-DMA bases in SGPRs)
             const uint4* b = uniform_ptr(b_cur);
-#ifndef WV_H16W_ABLATE_NO_A
             {
                 const uint32_t kofs = (uint32_t)(fc * 1024);
                 glds16(Xb + rbase[0] + kofs, dst);
                 glds16(Xb + rbase[1] + kofs, dst + 8 * 1024);
             }
-#endif
-#ifndef WV_H16W_ABLATE_NO_B
 #pragma unroll
             for (int j = 0; j < KC; ++j)
                 glds16s(uniform_ptr(b + j * gstride), (uint32_t)(lane * 16), dst + (uint32_t)(St::A_U4 * 16 + 8 * j * 1024));
-#endif
             if (fc == 0) {
                 if (p.rowidx) {
                     const uint64_t tn = tile + 1 < p.ntiles_real ? tile + 1 : p.ntiles_real - 1;
@@ -1013,22 +985,9 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
             // most OPS of this wave's ops still outstanding -- chunk g + 1's
             // blocks are its first OPS (its extras, issued after them, may
             // then have to land as well: a chunk's compute later, long done)
-#if defined(WV_H16W_ABLATE_NO_A) && defined(WV_H16W_ABLATE_NO_B)
-            vm_wait(0);
-#elif defined(WV_H16W_ABLATE_NO_A)
-            if (g + 1 < nchunks) vm_wait(KC);
-            else vm_wait(0);
-#elif defined(WV_H16W_ABLATE_NO_B)
-            if (g + 1 < nchunks) vm_wait(2);
-            else vm_wait(0);
-#else
             if (g + 1 < nchunks) vm_wait(St::OPS);
             else vm_wait(0);
-#endif
             block_barrier();
-#ifdef WV_H16W_FILL_EARLY
-            if (g + 2 < nchunks) fill_next(stg == 0 ? 2 : stg - 1);
-#endif
             const uint4* st = lds + stg * St::U4;
             if (c == 0) {
                 // C-in: s|x|^2 of the wave's rows (L2) or zero
@@ -1057,10 +1016,9 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
                 const half8 b1 = __builtin_bit_cast(half8, st[St::A_U4 + ((2 * qq + 1) * KC + k) * 64 + lane]);
                 // row 32 G + l31's chunk 2 k + khalf (swizzled slot)
                 const int aslot = 4 * l31 + ((2 * k + khalf) ^ ((l31 >> 2) & 3));
-#ifndef WV_H16W_JIT_READS
                 // every operand of the k-step read before its first MFMA: the
-                // scheduler otherwise reuses one A register set, each A read
-                // then waits for the MFMAs of the last (lgkmcnt(0) per MFMA
+                // scheduler otherwise reused one A register set, each A read
+                // then waited for the MFMAs of the last (lgkmcnt(0) per MFMA
                 // pair: the LDS latency exposed RG times per k-step)
                 half8 a[RG];
 #pragma unroll
@@ -1071,15 +1029,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
                     acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b0, acc[i][0], 0, 0, 0);
                     acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b1, acc[i][1], 0, 0, 0);
                 }
-#else
-#pragma unroll
-                for (int i = 0; i < RG; ++i) {
-                    const half8 a = __builtin_bit_cast(half8, st[128 * (RG * rh + i) + aslot]);
-                    acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b0, acc[i][0], 0, 0, 0);
-                    acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b1, acc[i][1], 0, 0, 0);
-                }
-#endif
-#ifndef WV_H16W_FILL_EARLY
                 // the next fill between this chunk's MFMAs, not beside the
                 // partner wave's fill after the barrier (2.33 -> 2.23 ms per
                 // C4-shaped pass, profiles/r03_h16w_fill_schedule_ablation.log)
@@ -1088,7 +1037,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
                     if (g + 2 < nchunks) fill_next(stg == 0 ? 2 : stg - 1);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#endif
             }
             const int tc = t;   // (the chunk just computed)
             stg = stg == 2 ? 0 : stg + 1;
@@ -1101,15 +1049,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
             const uint64_t row0 = tile * BN + WR * rh;
             const float pt0 = fminf(__shfl_xor(l0d[BF_KP - 1], 32, 64), tau0);
             const float pt1 = fminf(__shfl_xor(l1d[BF_KP - 1], 32, 64), tau1);
-#ifdef WV_H16W_ABLATE_NO_EPI
-            {
-                float z = pt0 + pt1;
-#pragma unroll
-                for (int i = 0; i < RG; ++i) z += acc[i][0][0] + acc[i][1][0];
-                if (z == 1234.5f) l0d[0] = 0.f;
-            }
-            continue;
-#endif
             // the wave's rows are the tile's words RG / 2 rh ..: 64 rows (two
             // row groups) per word
 #pragma unroll
@@ -1136,9 +1075,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
                 }
                 const uint32_t rb = (uint32_t)r0 + 4 * khalf;
                 WV_DBG_COUNT(0)
-#ifdef WV_H16W_ABLATE_NO_EXTRACT
-                if (fminf(fminf(min16(A0), min16(B0)), fminf(min16(A1), min16(B1))) == 1234.5f) l0d[0] = pt0;
-#else
                 // insertion of a column's minimum (wv_topk.h min_extract)
                 auto xt = [&](floatx16& A, float (&ld)[BF_KP], uint32_t (&li)[BF_KP], float pt, uint32_t rr) {
                     const float th = fminf(ld[BF_KP - 1], pt);
@@ -1156,7 +1092,6 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
                 xt(B0, l0d, l0i, pt0, rb + 32);
                 xt(A1, l1d, l1i, pt1, rb);
                 xt(B1, l1d, l1i, pt1, rb + 32);
-#endif
             }
             // every tile while the lists fill, then every 4th
             if (running && (tc < 8 || (tc & 3) == 3)) publish();
@@ -1188,39 +1123,11 @@ __global__ __launch_bounds__(64) void wv_h16_seed_kernel(H16SeedParams p) {
     const int q = blockIdx.x;
     const int lane = threadIdx.x;
     if (q >= p.nq) return;
-    const int prod = p.prod ? p.prod : H_PROD;
-    const int n = bf_slots_of((uint64_t)(q / p.bq), p.ntiles, p.units_per_block) * prod;
-    const float* m = p.minima + (size_t)q * p.n_slots * prod;
+    const int n = bf_slots_of((uint64_t)(q / p.bq), p.ntiles, p.units_per_block) * H_PROD;
+    const float* m = p.minima + (size_t)q * p.n_slots * H_PROD;
     const float inv_s = 1.0f / (p.sx * p.qscale[0]);
     float mk = __builtin_inff();
-    if (p.ids) {
-        // list mode (n <= 256, k <= 64: the host's condition): every entry
-        // sorted by (key, id); the k-th a real row's, or none
-        const size_t off = (size_t)q * p.n_slots * prod;
-        uint64_t kk[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = 64 * j + lane;
-            const uint32_t id = e < n ? p.ids[off + e] : WV_NIL;
-            kk[j] = fin_key(id != WV_NIL ? p.minima[off + e] : FLT_MAX, id);
-        }
-        bitonic256_wave(kk, lane);
-        float d;
-        uint32_t id;
-        fin_unkey(kk[0], d, id);
-        const float dk = __shfl(d, p.k - 1, 64);
-        const uint32_t ik = (uint32_t)__shfl((int)id, p.k - 1, 64);
-        if (ik != WV_NIL) mk = dk;
-        // the 2 BF_KP smallest: one more slot of the main pass's lists (even
-        // ranks, odd ranks), after the query block's own slots
-        const int os = bf_slots_of((uint64_t)(q / p.bq), p.out_ntiles, p.out_upb);
-        const size_t ob = ((size_t)q * p.out_slots + os) * H_PROD * BF_KP;
-        if (lane < H_PROD * BF_KP) {
-            const size_t o = ob + (size_t)(lane & 1) * BF_KP + (lane >> 1);
-            p.out_d[o] = d;
-            p.out_id[o] = id;
-        }
-    } else if (n <= 256) {
+    if (n <= 256) {
         // the k-th smallest by a wave-wide bitonic sort of the (<= 256)
         // minima, element i = 64 j + lane in register j
         float v[4];
@@ -1290,9 +1197,6 @@ __global__ __launch_bounds__(64) void wv_h16_seed_kernel(H16SeedParams p) {
             tau = key + 2.f * eps;
             tau += 4.f * 5.9604645e-08f * (fabsf(key) + 2.f * eps) + 1e-3f * eps;   // this sum's rounding
         }
-        // (list mode: the list pass dropped keys above the minima pass's
-        // threshold, already in p.tau -- the thresholds only decrease)
-        if (p.ids) tau = fminf(tau, p.tau[q]);
         p.tau[q] = tau;
         if (p.gtau) p.gtau[q] = h16_key_enc(tau * (p.sx * p.qscale[0]));
     }
@@ -1551,8 +1455,7 @@ hipError_t wv_launch_bf_h16(const wv::H16Params* p, int ns, int seed, hipStream_
     const uint64_t total = (uint64_t)p->n_qblocks * p->ntiles;
     const unsigned nb = (unsigned)((total + p->units_per_block - 1) / p->units_per_block);
     if (nb == 0) return hipSuccess;
-    if (ns < 1 || ns > wv::H_NS_MAX || !p->X || !p->Q || !p->excl || !p->qscale || p->tile_stride < 1 ||
-        (p->out_slots && p->out_slots < p->n_slots) || (seed && (p->out_slots || p->tile_base)))
+    if (ns < 1 || ns > wv::H_NS_MAX || !p->X || !p->Q || !p->excl || p->tile_stride < 1)
         return hipErrorInvalidValue;
     const bool l2 = p->metric == WV_METRIC_L2;
     if (l2 && !p->xns) return hipErrorInvalidValue;
@@ -1607,25 +1510,21 @@ hipError_t wv_launch_bf_h16w(const wv::H16Params* p, hipStream_t s) {
     const unsigned nb = (unsigned)((total + p->units_per_block - 1) / p->units_per_block);
     if (nb == 0) return hipSuccess;
     if (p->ns < 2 * wv::HW_KC || p->ns > wv::HW_NS_MAX || p->ns % wv::HW_KC || !p->X || !p->Q || !p->excl ||
-        p->tile_stride != 1 || p->tile_base != 0 || p->out_slots != 0)
+        p->tile_stride != 1)
         return hipErrorInvalidValue;
     const bool l2 = p->metric == WV_METRIC_L2;
     if (l2 && !p->xns) return hipErrorInvalidValue;
-    if (p->wide_rows != 128) return hipErrorInvalidValue;
-    using St = wv::HWStage<128>;
+    using St = wv::HWStage;
     // + the gtau return slots and the row-list ring (2 slots x 8 waves x 2 x 64 ids)
     const size_t lds = ((size_t)wv::HW_STAGES * St::U4 + 2 * St::EX_U4) * 16 + 8 * 256 + 2 * 8 * 2 * 256;
-    if (l2) hipLaunchKernelGGL((wv::wv_bf_h16w_kernel<true, 128>), dim3(nb), dim3(512), lds, s, *p);
-    else hipLaunchKernelGGL((wv::wv_bf_h16w_kernel<false, 128>), dim3(nb), dim3(512), lds, s, *p);
+    if (l2) hipLaunchKernelGGL((wv::wv_bf_h16w_kernel<true>), dim3(nb), dim3(512), lds, s, *p);
+    else hipLaunchKernelGGL((wv::wv_bf_h16w_kernel<false>), dim3(nb), dim3(512), lds, s, *p);
     return hipGetLastError();
 }
 
 hipError_t wv_launch_h16_seed(const wv::H16SeedParams* p, hipStream_t s) {
     if (p->nq == 0) return hipSuccess;
     if (p->k < 1 || p->k > wv::BF_WIDE_KMAX) return hipErrorInvalidValue;
-    if (p->ids && (p->k > 64 || p->prod != wv::H_PROD * wv::BF_KP || (size_t)p->n_slots * p->prod > 256 ||
-                   !p->out_d || !p->out_id || p->out_slots < 1))
-        return hipErrorInvalidValue;
     hipLaunchKernelGGL(wv::wv_h16_seed_kernel, dim3(p->nq), dim3(64), 0, s, *p);
     return hipGetLastError();
 }

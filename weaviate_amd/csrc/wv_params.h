@@ -152,17 +152,12 @@ struct H16Params {
     const float* xns;         // s * |x|^2 per row (L2 only), padded to whole tiles
     const uint64_t* excl;     // excluded rows (tombstones, nil nodes, no vector): one word per tile
     const uint64_t* allow;    // shared allow bits (nullable): at least one word per tile
-    const float* tau;         // [nq] seed threshold in true key units (nullable): keys above it are dropped
-    const float* qscale;      // device scalar s_q (read at launch)
-    float sx;                 // corpus scale s_x
     uint64_t N;               // rows
     int nq, metric;
     int n_qblocks, n_slots;
     uint64_t ntiles, units_per_block;   // ntiles: tiles scanned (the sample's when tile_stride > 1)
     uint64_t ntiles_real;     // the wide-D pass: the corpus's tiles (ntiles, the unit grid per query block, may pad it)
-    int tile_stride;          // corpus tile = tile_base + scanned tile * tile_stride (seed pre-pass)
-    uint64_t tile_base;       // (the D <= 128 pass; 0 elsewhere)
-    int out_slots;            // list slots per query in out_d / out_id (0: n_slots)
+    int tile_stride;          // corpus tile = scanned tile * tile_stride (the seed pre-pass; 1 elsewhere)
     uint64_t clean_tiles;     // corpus tiles [0, clean_tiles) have no excluded row (no allow list either): no mask
     int locality;             // bit 1: XCD-contiguous workgroup ids
     const int* block_order;   // optional: XCD-contiguous position -> block (run_h16's block_order)
@@ -181,7 +176,6 @@ struct H16Params {
     float* gslot;             // [nq][2 n_slots] (xslot)
     int xslot;                // 1: use gslot instead of the gtau publish
     int ns;                   // 16-k steps of the images (the wide-D kernel: a multiple of HW_KC)
-    int wide_rows;            // the wide-D kernel's rows per wave: 128 (256-row tiles) or 64 (128-row tiles)
     // the wide-D kernel (round 5): X is h16w_index (row r's 64 B panels per
     // 16-row group) and its operand blocks are filled per lane; rowidx
     // (nullable): scan rows rowidx[0 .. N) (a compacted allow list, ascending,
@@ -196,12 +190,12 @@ struct H16Params {
 };
 
 // ---- f16 key pass for D > 128 (wv_bf_h16w_kernel, wv_h16.hip) --------------
-// Both operands stream through LDS in 64-k chunks (3 stages): 128 corpus rows
-// x 256 queries per 512-thread workgroup, 64 x 64 per wave; the tile epilogue
-// (mask, minima, extraction) runs once per D / 64 chunks.
-constexpr int HW_BN = 256;    // corpus rows per tile (wide_rows 128; 128 at wide_rows 64)
+// Both operands stream through LDS in 32-k chunks (3 stages): 256 corpus rows
+// x 256 queries per 512-thread workgroup, 128 x 64 per wave; the tile epilogue
+// (mask, minima, extraction) runs once per D / 32 chunks.
+constexpr int HW_BN = 256;    // corpus rows per tile
 constexpr int HW_BQ = 256;    // queries per block
-constexpr int HW_KC = 4;      // 16-k steps per chunk
+constexpr int HW_KC = 4;      // 16-k steps of image padding (ns a multiple of it); a chunk is HW_KC / 2 of them
 constexpr int HW_PROD = 4;    // lists per query per slot: 2 row halves x 2 lane halves
 constexpr int HW_NS_MAX = 64; // D <= 1024
 
@@ -238,18 +232,6 @@ struct H16SeedParams {
     float* tau;               // [nq] out: threshold in true key units (+inf: none)
     unsigned int* gtau;       // [nq] out (nullable): h16_key_enc(tau * s), the running threshold's start
     int bq;                   // queries per block of the pre-pass
-    int prod;                 // minima per query per slot (0: H_PROD)
-    // list mode (ids != nullptr; tau holds the minima pre-pass's thresholds,
-    // which the result never exceeds): `minima` are the list pre-pass's lists
-    // ([nq][n_slots][prod] entries, prod = H_PROD BF_KP), the key of each a
-    // distinct row; their 2 BF_KP smallest also go to the main pass's lists as
-    // one more slot (slot bf_slots_of(qb) of out_ntiles / out_upb, out_slots
-    // per query): even ranks to its first list, odd ranks to its second
-    const uint32_t* ids;
-    float* out_d;
-    uint32_t* out_id;
-    int out_slots;
-    uint64_t out_ntiles, out_upb;
 };
 
 struct BfFinParams {
@@ -260,7 +242,6 @@ struct BfFinParams {
     const float* qnorm;     // |q|^2 (L2) or |q| (dot, cosine)
     float xnorm_max;        // max |x| over the corpus (rounded up)
     int n_slots;            // list slots per query (BfParams.n_slots)
-    int extra_slot;         // 1: one more slot of lists after a query block's slots (the seed pre-pass's)
     uint64_t ntiles, units_per_block;
     int nq, D, ldx, ldq, metric, k;
     uint64_t id_base;       // global id of local id 0

@@ -28,7 +28,10 @@
  *    ids = id_base + local id (id_base set at creation, for corpus sharding).
  *  - The AllowList (adapters/repos/db/helpers/allow_list.go:19-118) crosses
  *    the boundary as a dense little-endian uint64 bitmap: bit i of word i/64
- *    set <=> docID i allowed.  allow_bits == NULL means "no filter".
+ *    set <=> docID i allowed.  allow_bits == NULL means "no filter".  The
+ *    _ids entry points (wv_search_batch_ids,
+ *    wv_search_by_vector_distance_batch_ids) take one list per query as
+ *    strictly ascending ids instead, and the device reads only the listed rows.
  *  - Results are ascending by distance; equal distances are ordered by id.
  *  - Thread safety: an index may be searched from many threads at once (calls
  *    on one index are serialised on its stream; wv_batcher coalesces
@@ -197,6 +200,38 @@ int wv_search_by_vector_distance_batch(wv_index *ix, const float *queries, int n
                                        int64_t max_limit, const uint64_t *allow_bits, uint64_t allow_nbits,
                                        uint64_t allow_stride_words, uint64_t *out_ids, float *out_dists,
                                        int64_t out_cap, int64_t *out_n);
+
+/* wv_search_by_vector_distance_batch with one allow list per query, as ids:
+ * query q may return only allow_ids[allow_offsets[q] .. allow_offsets[q+1]) --
+ * local ids, strictly ascending within a query (the AllowList's Slice()), as
+ * in wv_search_batch_ids.  The result -- ids, distance bits and out_n -- is
+ * that of wv_search_by_vector_distance_batch given per-query bitmaps with
+ * exactly those bits set.  All pointers are host memory and the call blocks.
+ * An empty range allows nothing (out_n = 0); an id past the rows or >= 2^31
+ * is skipped; a null index or offsets, nq < 0, out_cap < 0, offsets that do
+ * not start at 0 or decrease, and ids that do not ascend return WV_EINVAL
+ * before any device call.  No bitmap is built or counted on the host: flat or
+ * HNSW round 1 is decided per query from the list's length (search.go:64-79),
+ * and every query's threshold pass walks its list on the device, reading only
+ * the listed rows, into a segment of min(list length, WV_SBD_CAP) entries.  A
+ * batch whose segments sum past 2^26 entries (WV_SBD_IDS_MAX_ENTRIES, read
+ * per call; for tests) runs in consecutive chunks of queries.  The bitmap
+ * rows of the HNSW round-1 queries are scattered on the device.  A query
+ * whose within-target set outgrows its segment (more than WV_SBD_CAP rows),
+ * a PQ-compressed index and vectors wider than 8192 floats take the
+ * per-query wv_search_by_vector_distance over a bitmap row built for that
+ * query alone.  Not provided: a group variant
+ * (wv_group_search_by_vector_distance_batch takes bitmaps only) and a
+ * device-pointer variant. */
+int wv_search_by_vector_distance_batch_ids(wv_index *ix, const float *queries, int nq, const float *target_distances,
+                                           int64_t max_limit, const uint64_t *allow_ids,
+                                           const uint64_t *allow_offsets /* [nq+1] */, uint64_t *out_ids,
+                                           float *out_dists, int64_t out_cap, int64_t *out_n);
+/* The last wv_search_by_vector_distance_batch_ids on the index (nullable
+ * outputs): queries answered from the list pass, ids handed to it, queries
+ * whose round 1 was an HNSW search, queries sent down the per-query path. */
+int wv_last_sbd_ids_stats(wv_index *ix, uint64_t *list_queries, uint64_t *list_ids, uint64_t *hnsw_round1_queries,
+                          uint64_t *legacy_queries);
 
 /* Batched search of nq queries (row-major [nq][dim]).  ef <= 0 selects
  * searchTimeEF(k).  allow_bits may be NULL, one bitmap shared by the batch
@@ -368,7 +403,10 @@ int wv_batcher_search(wv_batcher *b, const float *vector, int k, const uint64_t 
 int wv_batcher_search_ids(wv_batcher *b, const float *vector, int k, int filtered, const uint64_t *allow_ids,
                           uint64_t n_allow, uint64_t *out_ids, float *out_dists, int32_t *out_n);
 /* SearchByVectorDistance through the micro-batcher: concurrent callers with
- * the same maxLimit coalesce into one wv_search_by_vector_distance_batch.
+ * the same maxLimit coalesce into one wv_search_by_vector_distance_batch; a
+ * batch on a single index whose requests all carry id lists that differ goes
+ * to wv_search_by_vector_distance_batch_ids as ids, with no bitmap row filled
+ * on the host (WV_BATCHER_IDS=0: bitmap rows, as for wv_batcher_search_ids).
  * out_cap entries at most are written; *out_n receives the full count. */
 int wv_batcher_search_distance_ids(wv_batcher *b, const float *vector, float target_distance, int64_t max_limit,
                                    int filtered, const uint64_t *allow_ids, uint64_t n_allow, uint64_t *out_ids,

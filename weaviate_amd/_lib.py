@@ -98,6 +98,9 @@ SIGNATURES = {
                                                C.POINTER(C.c_int64)]),
     "wv_search_by_vector_distance_batch": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp, C.c_uint64, C.c_uint64,
                                                      _vp, _vp, C.c_int64, _vp]),
+    "wv_search_by_vector_distance_batch_ids": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp,
+                                                         C.c_int64, _vp]),
+    "wv_last_sbd_ids_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
     "wv_search_batch": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp,
                                   _vp]),
     "wv_search_batch_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int,
@@ -122,6 +125,8 @@ SIGNATURES = {
     "wv_graph_destroy": (C.c_int, [_vp]),
     "wv_batcher_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "wv_batcher_search": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "wv_batcher_search_distance_ids": (C.c_int, [_vp, _vp, C.c_float, C.c_int64, C.c_int, _vp, C.c_uint64, _vp, _vp,
+                                                 C.c_int64, C.POINTER(C.c_int64)]),
     "wv_batcher_stats": (C.c_int, [_vp, _u64p, _u64p]),
     "wv_batcher_destroy": (C.c_int, [_vp]),
     "wv_group_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(WvConfig), C.c_uint64, C.c_int,

@@ -53,6 +53,10 @@ hipError_t wv_launch_hnsw_side(const wv::HnswParams* p, int waves_per_block, int
 hipError_t wv_launch_sbd_scan(const wv::SbdParams* p, hipStream_t s);
 hipError_t wv_sbd_sort(unsigned long long* keys, unsigned long long* tmp, const unsigned int* cnt, int nq, int cap,
                        int* offsets, void** scratch, size_t* scratch_cap, hipStream_t s);
+hipError_t wv_launch_sbd_ids(const wv::SbdIdsParams* p, hipStream_t s);
+hipError_t wv_sbd_ids_sort(unsigned long long* keys, unsigned long long* tmp, int n_keys, const unsigned int* cnt,
+                           int q0, int nq, const int* seg_beg, const int* seg_cap, int* ends, void** scratch,
+                           size_t* scratch_cap, hipStream_t s);
 hipError_t wv_launch_pq_encode(const float* X, int ldx, const uint64_t* ids, uint64_t n_rows, const wv::PqParams* pq,
                                uint8_t* codes, hipStream_t s);
 hipError_t wv_launch_pq_scan(const wv::PqScanParams* p, hipStream_t s);
@@ -302,6 +306,8 @@ struct wv_index {
     DevBuf q_in, q_norm, q_nrm2, q_scaled, cand_d, cand_id, fail, status, counters;
     // SearchByVectorDistance batches (wv_sbd.hip): targets, lists, counts, sort scratch
     DevBuf sbd_t, sbd_keys, sbd_tmp, sbd_cnt, sbd_off, sbd_q;
+    DevBuf sbd_seg;         // (the id-list route) a chunk's segment starts, lengths and ends
+    uint64_t sbd_ids_list_q = 0, sbd_ids_list_ids = 0, sbd_ids_hnsw_q = 0, sbd_ids_legacy_q = 0;   // the last call's routes
     void* sbd_scr = nullptr;
     size_t sbd_scr_cap = 0;
     DevBuf scan_d, scan_i, sort_d, sort_i, sort_tmp;
@@ -1763,7 +1769,8 @@ int wv_index_destroy(wv_index* ix) {
         b->release();
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     ix->allow_keep.release();
-    for (DevBuf* b : {&ix->sbd_t, &ix->sbd_keys, &ix->sbd_tmp, &ix->sbd_cnt, &ix->sbd_off, &ix->sbd_q}) b->release();
+    for (DevBuf* b : {&ix->sbd_t, &ix->sbd_keys, &ix->sbd_tmp, &ix->sbd_cnt, &ix->sbd_off, &ix->sbd_q, &ix->sbd_seg})
+        b->release();
     if (ix->sbd_scr) (void)hipFree(ix->sbd_scr);
     ix->sbd_scr = nullptr;
     ix->cimg16.release();
@@ -2551,6 +2558,103 @@ struct SlotLease {
         ix->slot_cv.notify_one();
     }
 };
+
+// the pinned slot grown to `need` bytes, with its event
+int slot_reserve(wv_index::HostSlot& sl, size_t need) {
+    if (sl.cap < need) {
+        if (sl.pin) HIP_TRY(hipHostFree(sl.pin));
+        sl.pin = nullptr;
+        sl.cap = 0;
+        const size_t want = std::max<size_t>(need + need / 4, 1 << 20);
+        HIP_TRY(hipHostMalloc(&sl.pin, want, hipHostMallocDefault));
+        sl.cap = want;
+    }
+    if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    return WV_OK;
+}
+
+// Per-query allow lists given as ids (wv_search_batch_ids and
+// wv_search_by_vector_distance_batch_ids; fn: the caller's name for the
+// messages).  The offsets' checks, before any device call:
+int ids_check_offsets(const std::string& fn, const uint64_t* allow_ids, const uint64_t* allow_offsets, int nq) {
+    if (allow_offsets[0] != 0) return fail(WV_EINVAL, fn + ": allow_offsets[0] must be 0");
+    for (int q = 0; q < nq; ++q)
+        if (allow_offsets[q + 1] < allow_offsets[q]) return fail(WV_EINVAL, fn + ": allow_offsets must not decrease");
+    if (allow_offsets[nq] && !allow_ids) return fail(WV_EINVAL, fn + ": null allow_ids");
+    return WV_OK;
+}
+
+// ... and the lists into the pinned slot: ids narrowed to u32 (capacity <
+// 2^31; larger ids name no row) at ids32, the kept lists' offsets at off
+// [nq + 1]; a list that does not strictly ascend is refused.
+int ids_stage(const std::string& fn, const uint64_t* allow_ids, const uint64_t* allow_offsets, int nq, uint32_t* ids32,
+              uint64_t* off) {
+    const uint64_t total = allow_offsets[nq];
+    // In an ascending list the ids >= 2^31 are a suffix: each list's kept
+    // length first (a list out of order is refused below, whatever was kept)
+    uint64_t pos = 0;
+    for (int q = 0; q < nq; ++q) {
+        off[q] = pos;
+        uint64_t m = allow_offsets[q + 1] - allow_offsets[q];
+        while (m && allow_ids[allow_offsets[q] + m - 1] >= (1ull << 31)) --m;
+        pos += m;
+    }
+    off[nq] = pos;
+    // one pass over the lists: the ascending check and the narrowing, in
+    // threads over equal shares of the ids when the batch is large (a 256 x
+    // 40,000 batch reads 80 MB: one core's pass cost more than the search)
+    auto narrow = [&](int q0, int q1) {
+        uint64_t bad = 0;
+        for (int q = q0; q < q1; ++q) {
+            const uint64_t* a = allow_ids + allow_offsets[q];
+            const uint64_t n = allow_offsets[q + 1] - allow_offsets[q], m = off[q + 1] - off[q];
+            uint32_t* o = ids32 + off[q];
+            for (uint64_t i = 0; i < m; ++i) o[i] = (uint32_t)a[i];
+            for (uint64_t i = 1; i < n; ++i) bad |= (uint64_t)(a[i] <= a[i - 1]);
+        }
+        return bad != 0;
+    };
+    bool bad = false;
+    const int nth = (int)std::min<uint64_t>(std::min(8, nq), total >> 18);
+    if (nth <= 1) {
+        bad = narrow(0, nq);
+    } else {
+        std::vector<std::thread> th;
+        std::vector<char> tb((size_t)nth, 0);
+        int q0 = 0;
+        for (int t = 0; t < nth; ++t) {
+            int q1 = q0;
+            const uint64_t until = t == nth - 1 ? total : total / nth * (t + 1);
+            while (q1 < nq && (allow_offsets[q1 + 1] <= until || t == nth - 1)) ++q1;
+            th.emplace_back([&, t, q0, q1] { tb[t] = narrow(q0, q1); });
+            q0 = q1;
+        }
+        for (auto& x : th) x.join();
+        for (char c : tb) bad |= c != 0;
+    }
+    if (bad) return fail(WV_EINVAL, fn + ": allow ids must be strictly ascending within a query");
+    return WV_OK;
+}
+
+// the staged lists and their offsets to the device (fi_ids, fi_off)
+int ids_upload(wv_index* ix, const uint32_t* ids32, const uint64_t* off, int nq, hipStream_t s) {
+    const uint64_t kept = off[nq];
+    const size_t fb = ((size_t)nq + 1) * 8;
+    HIP_TRY(ix->fi_ids.ensure(std::max<size_t>(kept * 4, 4)));
+    HIP_TRY(ix->fi_off.ensure(fb));
+    if (kept) HIP_TRY(hipMemcpyAsync(ix->fi_ids.p, ids32, kept * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ix->fi_off.p, off, fb, hipMemcpyHostToDevice, s));
+    return WV_OK;
+}
+
+// chunks of a list for a grid of (ns queries, chunks): enough workgroups to
+// fill the machine, at least 512 ids each; whole wave rounds (256 ids)
+void ids_chunks(const wv_index* ix, int ns, uint64_t max_len, uint64_t* chunk_len, uint64_t* n_chunks) {
+    uint64_t nc = std::max<uint64_t>(1, (2 * (uint64_t)ix->n_cus + ns - 1) / ns);
+    nc = std::max<uint64_t>(1, std::min(nc, (max_len + 511) / 512));
+    *chunk_len = std::max<uint64_t>(256, ((max_len + nc - 1) / nc + 255) / 256 * 256);
+    *n_chunks = std::max<uint64_t>(1, (max_len + *chunk_len - 1) / *chunk_len);
+}
 }  // namespace
 
 int wv_search_batch(wv_index* ix, const float* queries, int nq, int k, int ef, const uint64_t* allow_bits,
@@ -2628,12 +2732,8 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
     if (check(ix)) return fail(WV_EINVAL, "wv_search_batch_ids: null index");
     if (nq && (!queries || !out_ids || !out_dists || !out_n))
         return fail(WV_EINVAL, "wv_search_batch_ids: null queries or outputs");
-    if (allow_offsets[0] != 0) return fail(WV_EINVAL, "wv_search_batch_ids: allow_offsets[0] must be 0");
-    for (int q = 0; q < nq; ++q)
-        if (allow_offsets[q + 1] < allow_offsets[q])
-            return fail(WV_EINVAL, "wv_search_batch_ids: allow_offsets must not decrease");
+    if (int rc = ids_check_offsets("wv_search_batch_ids", allow_ids, allow_offsets, nq)) return rc;
     const uint64_t total = allow_offsets[nq];
-    if (total && !allow_ids) return fail(WV_EINVAL, "wv_search_batch_ids: null allow_ids");
     if (nq == 0) return WV_OK;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t qb = (size_t)nq * ix->dim * 4, lb = (size_t)total * 4, fb = ((size_t)nq + 1) * 8,
@@ -2643,63 +2743,12 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
     HIP_TRY(hipSetDevice(ix->cfg.device));
     SlotLease lease(ix);
     wv_index::HostSlot& sl = *lease.sl;
-    if (sl.cap < need) {
-        if (sl.pin) HIP_TRY(hipHostFree(sl.pin));
-        sl.pin = nullptr;
-        sl.cap = 0;
-        const size_t want = std::max<size_t>(need + need / 4, 1 << 20);
-        HIP_TRY(hipHostMalloc(&sl.pin, want, hipHostMallocDefault));
-        sl.cap = want;
-    }
-    if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    if (int rc = slot_reserve(sl, need)) return rc;
     char* pin = static_cast<char*>(sl.pin);
     std::memcpy(pin, queries, qb);
-    // ids narrowed to u32 (capacity < 2^31; larger ids name no row)
     uint32_t* ids32 = reinterpret_cast<uint32_t*>(pin + o_l);
     uint64_t* off = reinterpret_cast<uint64_t*>(pin + o_f);
-    // In an ascending list the ids >= 2^31 are a suffix: each list's kept
-    // length first (a list out of order is refused below, whatever was kept)
-    uint64_t pos = 0;
-    for (int q = 0; q < nq; ++q) {
-        off[q] = pos;
-        uint64_t m = allow_offsets[q + 1] - allow_offsets[q];
-        while (m && allow_ids[allow_offsets[q] + m - 1] >= (1ull << 31)) --m;
-        pos += m;
-    }
-    off[nq] = pos;
-    // one pass over the lists: the ascending check and the narrowing, in
-    // threads over equal shares of the ids when the batch is large (a 256 x
-    // 40,000 batch reads 80 MB: one core's pass cost more than the search)
-    auto narrow = [&](int q0, int q1) {
-        uint64_t bad = 0;
-        for (int q = q0; q < q1; ++q) {
-            const uint64_t* a = allow_ids + allow_offsets[q];
-            const uint64_t n = allow_offsets[q + 1] - allow_offsets[q], m = off[q + 1] - off[q];
-            uint32_t* o = ids32 + off[q];
-            for (uint64_t i = 0; i < m; ++i) o[i] = (uint32_t)a[i];
-            for (uint64_t i = 1; i < n; ++i) bad |= (uint64_t)(a[i] <= a[i - 1]);
-        }
-        return bad != 0;
-    };
-    bool bad = false;
-    const int nth = (int)std::min<uint64_t>(std::min(8, nq), total >> 18);
-    if (nth <= 1) {
-        bad = narrow(0, nq);
-    } else {
-        std::vector<std::thread> th;
-        std::vector<char> tb((size_t)nth, 0);
-        int q0 = 0;
-        for (int t = 0; t < nth; ++t) {
-            int q1 = q0;
-            const uint64_t until = t == nth - 1 ? total : total / nth * (t + 1);
-            while (q1 < nq && (allow_offsets[q1 + 1] <= until || t == nth - 1)) ++q1;
-            th.emplace_back([&, t, q0, q1] { tb[t] = narrow(q0, q1); });
-            q0 = q1;
-        }
-        for (auto& x : th) x.join();
-        for (char c : tb) bad |= c != 0;
-    }
-    if (bad) return fail(WV_EINVAL, "wv_search_batch_ids: allow ids must be strictly ascending within a query");
+    if (int rc = ids_stage("wv_search_batch_ids", allow_ids, allow_offsets, nq, ids32, off)) return rc;
     {
         std::lock_guard<std::mutex> g(ix->mu);
         HIP_TRY(hipSetDevice(ix->cfg.device));
@@ -2707,10 +2756,8 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
         const float* dq = nullptr;
         int rc = stage_queries(ix, reinterpret_cast<const float*>(pin), nq, &dq, s);
         if (rc) return rc;
-        HIP_TRY(ix->fi_ids.ensure(std::max<size_t>(pos * 4, 4)));
-        HIP_TRY(ix->fi_off.ensure(fb));
-        if (pos) HIP_TRY(hipMemcpyAsync(ix->fi_ids.p, ids32, pos * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ix->fi_off.p, off, fb, hipMemcpyHostToDevice, s));
+        rc = ids_upload(ix, ids32, off, nq, s);
+        if (rc) return rc;
         HIP_TRY(ix->out_ids.ensure(ib));
         HIP_TRY(ix->out_d.ensure(db));
         HIP_TRY(ix->out_n.ensure(nb));
@@ -2747,12 +2794,8 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
         ix->fi_timed = false;
         if (!sel[0].empty()) {
             const int ns = (int)sel[0].size();
-            // chunks of a list: enough workgroups to fill the machine, at
-            // least 512 ids each; whole wave rounds (256 ids)
-            uint64_t nc = std::max<uint64_t>(1, (2 * (uint64_t)ix->n_cus + ns - 1) / ns);
-            nc = std::max<uint64_t>(1, std::min(nc, (sp_max + 511) / 512));
-            const uint64_t chunk_len = std::max<uint64_t>(256, ((sp_max + nc - 1) / nc + 255) / 256 * 256);
-            nc = std::max<uint64_t>(1, (sp_max + chunk_len - 1) / chunk_len);
+            uint64_t chunk_len = 0, nc = 0;
+            ids_chunks(ix, ns, sp_max, &chunk_len, &nc);
             wv::FlatIdsParams fp{};
             fp.X = ix->vecs.as<float>();
             fp.Q = dq;
@@ -2943,6 +2986,56 @@ int64_t sbd_exact_rounds(int r0, int64_t Qn, int64_t A, int64_t n, int64_t max_l
     }
     return kept;
 }
+
+// whether an HNSW round 1 (its hi distances, ascending) lets the deepening go on
+bool sbd_r1_continues(const float* r1_d, int64_t hi, float t, int64_t max_limit) {
+    return hi > 0 && r1_d[hi - 1] <= t && (max_limit < 0 || 1100 <= max_limit);
+}
+
+// entries of a query's sorted list that the rounds keep, from its counts
+// cnt3 = {|Q|, A, n}; r1_d / r1_n: its HNSW round 1 (r1_d null: round 1 is
+// exact too).  (An HNSW round 1 that ends the deepening needs no list.)
+int64_t sbd_list_need(const float* r1_d, int32_t r1_n, float t, int64_t max_limit, const unsigned int* cnt3) {
+    if (r1_d && !sbd_r1_continues(r1_d, std::min<int64_t>(100, r1_n), t, max_limit)) return 0;
+    const int64_t kept = sbd_exact_rounds(r1_d ? 2 : 1, cnt3[0], cnt3[1], cnt3[2], max_limit);
+    return std::min<int64_t>(kept, cnt3[0]);
+}
+
+// a query's answer: the qualifying prefix of its HNSW round 1 (r1_d non-null),
+// then the kept entries of its sorted list, decoded; returns the count
+int64_t sbd_emit(const uint64_t* r1_ids, const float* r1_d, int32_t r1_n, float t, int64_t max_limit,
+                 const std::vector<unsigned long long>& list, uint64_t id_base, uint64_t* out_ids, float* out_dists,
+                 int64_t out_cap) {
+    int64_t m = 0;
+    auto put = [&](uint64_t id, float d) {
+        if (m < out_cap) { out_ids[m] = id; out_dists[m] = d; }
+        m++;
+    };
+    auto qual = [&](float d) { return d <= t || std::fabs((double)d - (double)t) <= 1e-6; };
+    bool exact_more = true;
+    if (r1_d) {
+        // round 1 from the HNSW search: its qualifying prefix, and whether
+        // the deepening continues
+        const int64_t hi = std::min<int64_t>(100, r1_n);
+        for (int64_t j = 0; j < hi; ++j) {
+            const float d = r1_d[j];
+            if (!qual(d)) break;
+            put(r1_ids[j], d);
+        }
+        exact_more = sbd_r1_continues(r1_d, hi, t, max_limit);
+    }
+    if (exact_more) {
+        for (int64_t j = r1_d ? 100 : 0; j < (int64_t)list.size(); ++j) {
+            const unsigned long long key = list[j];
+            uint32_t u = (uint32_t)(key >> 32);
+            u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+            float d;
+            std::memcpy(&d, &u, 4);
+            put(id_base + (uint32_t)key, d);
+        }
+    }
+    return m;
+}
 }  // namespace
 
 int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int nq, const float* targets,
@@ -3077,21 +3170,13 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
             // the sorted lists, as far as the rounds keep them (and the caller
             // takes them)
             std::vector<int64_t> need(nq, 0);
-            std::vector<char> is_h(nq, 0);
-            for (int q : hnsw_q) is_h[q] = 1;
             std::vector<int> hs(nq, -1);
             for (int i = 0; i < nh; ++i) hs[hnsw_q[i]] = i;
             for (int q = 0; q < nq; ++q) {
-                const int64_t Qn = cnt[3 * q], A = cnt[3 * q + 1], n = cnt[3 * q + 2];
-                if (is_h[q]) {   // (an HNSW round 1 that ends the deepening needs no list)
-                    const int i = hs[q];
-                    const int64_t hi = std::min<int64_t>(100, r1_n[i]);
-                    if (!(hi > 0 && r1_d[(size_t)i * 100 + hi - 1] <= targets[q] && (max_limit < 0 || 1100 <= max_limit)))
-                        continue;
-                }
-                const int64_t kept = sbd_exact_rounds(is_h[q] ? 2 : 1, Qn, A, n, max_limit);
-                need[q] = std::min<int64_t>(kept, Qn);
-                if (Qn > cap && need[q] > 0) { legacy.push_back(q); need[q] = 0; continue; }
+                const int i = hs[q];
+                need[q] = sbd_list_need(i >= 0 ? r1_d.data() + (size_t)i * 100 : nullptr, i >= 0 ? r1_n[i] : 0,
+                                        targets[q], max_limit, cnt.data() + 3 * (size_t)q);
+                if ((int64_t)cnt[3 * q] > cap && need[q] > 0) { legacy.push_back(q); need[q] = 0; continue; }
                 if (need[q] > 0) {
                     lists[q].resize(need[q]);
                     HIP_TRY(hipMemcpyAsync(lists[q].data(), ix->sbd_tmp.as<unsigned long long>() + (size_t)q * cap,
@@ -3102,41 +3187,13 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
         }
         std::vector<int> hslot(nq, -1);
         for (int i = 0; i < nh; ++i) hslot[hnsw_q[i]] = i;
-        const uint64_t id_base = ix->cfg.id_base;
         for (int q = 0; q < nq; ++q) {
             if (std::find(legacy.begin(), legacy.end(), q) != legacy.end()) continue;
-            const float t = targets[q];
-            int64_t m = 0;
-            auto put = [&](uint64_t id, float d) {
-                if (m < out_cap) { out_ids[(size_t)q * out_cap + m] = id; out_dists[(size_t)q * out_cap + m] = d; }
-                m++;
-            };
-            auto qual = [&](float d) { return d <= t || std::fabs((double)d - (double)t) <= 1e-6; };
-            bool exact_more = true;
-            if (hslot[q] >= 0) {
-                // round 1 from the HNSW search: its qualifying prefix, and
-                // whether the deepening continues
-                const int i = hslot[q];
-                const int64_t hi = std::min<int64_t>(100, r1_n[i]);
-                for (int64_t j = 0; j < hi; ++j) {
-                    const float d = r1_d[(size_t)i * 100 + j];
-                    if (!qual(d)) break;
-                    put(r1_ids[(size_t)i * 100 + j], d);
-                }
-                exact_more = hi > 0 && r1_d[(size_t)i * 100 + hi - 1] <= t && (max_limit < 0 || 1100 <= max_limit);
-            }
-            if (exact_more) {
-                const int64_t from = hslot[q] >= 0 ? 100 : 0;
-                for (int64_t j = from; j < (int64_t)lists[q].size(); ++j) {
-                    const unsigned long long key = lists[q][j];
-                    uint32_t u = (uint32_t)(key >> 32);
-                    u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-                    float d;
-                    std::memcpy(&d, &u, 4);
-                    put(id_base + (uint32_t)key, d);
-                }
-            }
-            out_n[q] = m;
+            const int i = hslot[q];
+            out_n[q] = sbd_emit(i >= 0 ? r1_ids.data() + (size_t)i * 100 : nullptr,
+                                i >= 0 ? r1_d.data() + (size_t)i * 100 : nullptr, i >= 0 ? r1_n[i] : 0, targets[q],
+                                max_limit, lists[q], ix->cfg.id_base, out_ids + (size_t)q * out_cap,
+                                out_dists + (size_t)q * out_cap, out_cap);
         }
     }
     for (int q : legacy) {
@@ -3145,6 +3202,265 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                                               out_cap ? out_dists + (size_t)q * out_cap : nullptr, out_cap, out_n + q);
         if (rc) return rc;
     }
+    return WV_OK;
+}
+
+// wv_search_by_vector_distance_batch with one allow list per query, as ids.
+// Every query's threshold pass walks its list (sbd_ids_kernel) into a segment
+// of min(list length, WV_SBD_CAP) keys; the segments of a chunk of queries lie
+// back to back and are sorted by one segmented sort, and a batch whose
+// segments sum past WV_SBD_IDS_MAX_ENTRIES (2^26) runs in consecutive chunks
+// of queries.  Flat or HNSW round 1 is decided from the list's length; the
+// HNSW queries' bitmap rows are scattered on the device.  The host arithmetic
+// is that of the bitmap route.
+int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, int nq, const float* targets,
+                                           int64_t max_limit, const uint64_t* allow_ids,
+                                           const uint64_t* allow_offsets, uint64_t* out_ids, float* out_dists,
+                                           int64_t out_cap, int64_t* out_n) {
+    const std::string fn = "wv_search_by_vector_distance_batch_ids";
+    if (nq < 0) return fail(WV_EINVAL, fn + ": nq < 0");
+    if (out_cap < 0) return fail(WV_EINVAL, fn + ": out_cap < 0");
+    if (!allow_offsets) return fail(WV_EINVAL, fn + ": null allow_offsets");
+    if (check(ix)) return fail(WV_EINVAL, fn + ": null index");
+    if (nq && (!queries || !targets || !out_n)) return fail(WV_EINVAL, fn + ": null queries, targets or out_n");
+    if (nq && out_cap && (!out_ids || !out_dists)) return fail(WV_EINVAL, fn + ": null outputs");
+    if (int rc = ids_check_offsets(fn, allow_ids, allow_offsets, nq)) return rc;
+    if (nq == 0) return WV_OK;
+    const uint64_t total = allow_offsets[nq];
+    int cap = 16384;
+    if (const char* e = std::getenv("WV_SBD_CAP")) cap = std::max(128, std::atoi(e));
+    uint64_t max_entries = 1ull << 26;
+    if (const char* e = std::getenv("WV_SBD_IDS_MAX_ENTRIES")) max_entries = std::strtoull(e, nullptr, 10);
+    max_entries = std::min<uint64_t>(std::max<uint64_t>(max_entries, 1), 0x7FFFFFFFull);
+    std::vector<int> legacy;   // queries for the per-query path
+    std::vector<int> hnsw_q;   // queries whose round 1 is an HNSW search
+    std::vector<int> hslot(nq, -1);
+    std::vector<uint64_t> r1_ids;
+    std::vector<float> r1_d;
+    std::vector<int32_t> r1_n;
+    std::vector<std::vector<unsigned long long>> lists(nq);
+    uint64_t N = 0;
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    {
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t qb = (size_t)nq * ix->dim * 4, lb = (size_t)total * 4, fb = ((size_t)nq + 1) * 8,
+                     tb = (size_t)nq * 4;
+        const size_t o_l = al(qb), o_f = o_l + al(lb), o_t = o_f + al(fb), need = o_t + al(tb);
+        SlotLease lease(ix);
+        wv_index::HostSlot& sl = *lease.sl;
+        if (int rc = slot_reserve(sl, need)) return rc;
+        char* pin = static_cast<char*>(sl.pin);
+        std::memcpy(pin, queries, qb);
+        std::memcpy(pin + o_t, targets, tb);
+        uint32_t* ids32 = reinterpret_cast<uint32_t*>(pin + o_l);
+        uint64_t* off = reinterpret_cast<uint64_t*>(pin + o_f);
+        if (int rc = ids_stage(fn, allow_ids, allow_offsets, nq, ids32, off)) return rc;
+        std::lock_guard<std::mutex> g(ix->mu);
+        HIP_TRY(hipSetDevice(ix->cfg.device));
+        hipStream_t s = ix->stream;
+        N = ix->n_rows;
+        ix->sbd_ids_list_q = ix->sbd_ids_list_ids = ix->sbd_ids_hnsw_q = ix->sbd_ids_legacy_q = 0;
+        if (ix->pq_on || ix->dpad > wv::FLAT_IDS_DPAD_MAX) {
+            // a compressed index ranks by the PQ distance, and the kernel
+            // keeps the query row in LDS: the per-query path
+            for (int q = 0; q < nq; ++q) legacy.push_back(q);
+        } else {
+            int rc = refresh_bitmaps(ix);
+            if (rc) return rc;
+            // the queries staged, and kept beside round 1's searches
+            const float* dq = nullptr;
+            rc = stage_queries(ix, reinterpret_cast<const float*>(pin), nq, &dq, s);
+            if (rc) return rc;
+            HIP_TRY(ix->sbd_q.ensure((size_t)nq * ix->dpad * 4));
+            HIP_TRY(hipMemcpyAsync(ix->sbd_q.p, dq, (size_t)nq * ix->dpad * 4, hipMemcpyDeviceToDevice, s));
+            rc = ids_upload(ix, ids32, off, nq, s);
+            if (rc) return rc;
+            HIP_TRY(ix->sbd_t.ensure(tb));
+            HIP_TRY(hipMemcpyAsync(ix->sbd_t.p, pin + o_t, tb, hipMemcpyHostToDevice, s));
+            HIP_TRY(ix->sbd_cnt.ensure((size_t)nq * 12));
+            HIP_TRY(hipMemsetAsync(ix->sbd_cnt.p, 0, (size_t)nq * 12, s));
+            // flat or HNSW round 1, from the list's length (search.go:64-79)
+            const bool can_hnsw = ix->has_graph && search_time_ef(ix->cfg, 100) <= wv::HNSW_EF_MAX;
+            for (int q = 0; q < nq; ++q) {
+                const uint64_t L = allow_offsets[q + 1] - allow_offsets[q];
+                const bool flat = !can_hnsw || (!ix->cfg.forbid_flat && (int64_t)L < ix->cfg.flat_search_cutoff);
+                if (!flat) {
+                    hslot[q] = (int)hnsw_q.size();
+                    hnsw_q.push_back(q);
+                }
+            }
+            const int nh = (int)hnsw_q.size();
+            r1_ids.resize((size_t)std::max(nh, 1) * 100);
+            r1_d.resize((size_t)std::max(nh, 1) * 100);
+            r1_n.resize(std::max(nh, 1));
+            std::vector<unsigned int> cnt(3 * (size_t)nq);
+            std::vector<int> segs;   // a chunk's segment starts, then their lengths
+            std::vector<unsigned long long> sorted;   // a chunk's sorted keys, when one copy fetches them
+            for (int q0 = 0; q0 < nq;) {
+                // the chunk [q0, q1): segments back to back, at most max_entries keys
+                segs.clear();
+                uint64_t sum = 0, max_len = 0;
+                int q1 = q0;
+                for (; q1 < nq; ++q1) {
+                    const uint64_t len = off[q1 + 1] - off[q1], seg = std::min<uint64_t>(len, (uint64_t)cap);
+                    if (q1 > q0 && sum + seg > max_entries) break;
+                    segs.push_back((int)sum);
+                    sum += seg;
+                    max_len = std::max(max_len, len);
+                }
+                const int nqc = q1 - q0, n_keys = (int)sum;
+                for (int q = q0; q < q1; ++q) segs.push_back((int)std::min<uint64_t>(off[q + 1] - off[q], (uint64_t)cap));
+                if (n_keys > 0) {
+                    HIP_TRY(ix->sbd_seg.ensure((size_t)nqc * 12));
+                    HIP_TRY(hipMemcpyAsync(ix->sbd_seg.p, segs.data(), (size_t)nqc * 8, hipMemcpyHostToDevice, s));
+                    HIP_TRY(ix->sbd_keys.ensure((size_t)n_keys * 8));
+                    HIP_TRY(ix->sbd_tmp.ensure((size_t)n_keys * 8));
+                    uint64_t chunk_len = 0, nc = 0;
+                    ids_chunks(ix, nqc, max_len, &chunk_len, &nc);
+                    while (nc > 65535) {
+                        chunk_len *= 2;
+                        nc = (max_len + chunk_len - 1) / chunk_len;
+                    }
+                    wv::SbdIdsParams sp{};
+                    sp.X = ix->vecs.as<float>();
+                    sp.Q = ix->sbd_q.as<float>();
+                    sp.target = ix->sbd_t.as<float>();
+                    sp.excl = ix->excl.as<uint64_t>();
+                    sp.excl_nbits = ix->capacity;
+                    sp.ids = ix->fi_ids.as<uint32_t>();
+                    sp.off = ix->fi_off.as<uint64_t>();
+                    sp.seg_beg = ix->sbd_seg.as<int>();
+                    sp.seg_cap = ix->sbd_seg.as<int>() + nqc;
+                    sp.n_rows = N;
+                    sp.chunk_len = chunk_len;
+                    sp.q0 = q0;
+                    sp.nq = nqc;
+                    sp.n_chunks = (int)nc;
+                    sp.D = ix->dim;
+                    sp.dpad = ix->dpad;
+                    sp.ldx = ix->ldx;
+                    sp.metric = ix->metric;
+                    sp.keys = ix->sbd_keys.as<unsigned long long>();
+                    sp.cnt = ix->sbd_cnt.as<unsigned int>();
+                    HIP_TRY(wv_launch_sbd_ids(&sp, s));
+                    HIP_TRY(wv_sbd_ids_sort(sp.keys, ix->sbd_tmp.as<unsigned long long>(), n_keys, sp.cnt, q0, nqc,
+                                            sp.seg_beg, sp.seg_cap, ix->sbd_seg.as<int>() + 2 * nqc, &ix->sbd_scr,
+                                            &ix->sbd_scr_cap, s));
+                }
+                if (q0 == 0 && nh) {
+                    // round 1 of the HNSW queries, beside the first chunk's
+                    // pass: their bitmap rows scattered from the ids into
+                    // bounded scratch, then SearchByVector(limit 100)
+                    HIP_TRY(ix->fi_sel.ensure((size_t)nh * 4));
+                    HIP_TRY(hipMemcpyAsync(ix->fi_sel.p, hnsw_q.data(), (size_t)nh * 4, hipMemcpyHostToDevice, s));
+                    const uint64_t words = std::max<uint64_t>(1, (N + 63) / 64);
+                    const size_t rows_cap =
+                        (size_t)std::max<uint64_t>(1, std::min<uint64_t>(65535, (1ull << 30) / (words * 8)));
+                    for (size_t c0 = 0; c0 < (size_t)nh; c0 += rows_cap) {
+                        const int n = (int)std::min(rows_cap, (size_t)nh - c0);
+                        const int32_t* d_sel = ix->fi_sel.as<int32_t>() + c0;
+                        uint64_t ml = 0;
+                        for (int i = 0; i < n; ++i) ml = std::max(ml, off[hnsw_q[c0 + i] + 1] - off[hnsw_q[c0 + i]]);
+                        HIP_TRY(ix->fi_q.ensure((size_t)n * ix->dpad * 4));
+                        HIP_TRY(ix->fi_bits.ensure((size_t)n * words * 8));
+                        HIP_TRY(ix->fi_oid.ensure((size_t)n * 100 * 8));
+                        HIP_TRY(ix->fi_od.ensure((size_t)n * 100 * 4));
+                        HIP_TRY(ix->fi_on.ensure((size_t)n * 4));
+                        hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(128), 0, s, ix->sbd_q.as<float>(), ix->dpad,
+                                           d_sel, n, ix->dpad, ix->fi_q.as<float>(), ix->dpad);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipMemsetAsync(ix->fi_bits.p, 0, (size_t)n * words * 8, s));
+                        HIP_TRY(wv_launch_ids_to_bits(ix->fi_ids.as<uint32_t>(), ix->fi_off.as<uint64_t>(), d_sel, n, ml,
+                                                      N, words, ix->fi_bits.as<uint64_t>(), s));
+                        rc = search_core(ix, ix->fi_q.as<float>(), n, 100, 0, ix->fi_bits.as<uint64_t>(),
+                                         std::max<uint64_t>(N, 1), words, WV_MODE_HNSW, ix->fi_oid.as<uint64_t>(),
+                                         ix->fi_od.as<float>(), ix->fi_on.as<int32_t>(), s);
+                        if (rc) return rc;
+                        HIP_TRY(hipMemcpyAsync(r1_ids.data() + c0 * 100, ix->fi_oid.p, (size_t)n * 100 * 8,
+                                               hipMemcpyDeviceToHost, s));
+                        HIP_TRY(hipMemcpyAsync(r1_d.data() + c0 * 100, ix->fi_od.p, (size_t)n * 100 * 4,
+                                               hipMemcpyDeviceToHost, s));
+                        HIP_TRY(hipMemcpyAsync(r1_n.data() + c0, ix->fi_on.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+                    }
+                }
+                HIP_TRY(hipMemcpyAsync(cnt.data() + 3 * (size_t)q0, ix->sbd_cnt.as<unsigned int>() + 3 * (size_t)q0,
+                                       (size_t)nqc * 12, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                // the sorted lists, as far as the rounds keep them: the
+                // segments lie back to back, so a chunk of short segments
+                // comes over in one copy (a copy per query cost more than the
+                // pass at 1024 queries), long ones each on its own
+                int64_t span = 0;   // keys up to the last kept entry
+                for (int q = q0; q < q1; ++q) {
+                    const int i = hslot[q];
+                    const int64_t need = sbd_list_need(i >= 0 ? r1_d.data() + (size_t)i * 100 : nullptr,
+                                                       i >= 0 ? r1_n[i] : 0, targets[q], max_limit,
+                                                       cnt.data() + 3 * (size_t)q);
+                    if (need <= 0) continue;
+                    if ((int64_t)cnt[3 * (size_t)q] > segs[nqc + q - q0]) {
+                        legacy.push_back(q);
+                        continue;
+                    }
+                    lists[q].resize(need);
+                    span = std::max<int64_t>(span, segs[q - q0] + need);
+                }
+                const bool one_copy = span * 8 <= (int64_t)(8 << 20);
+                if (one_copy && span) {
+                    sorted.resize(span);
+                    HIP_TRY(hipMemcpyAsync(sorted.data(), ix->sbd_tmp.p, 8 * (size_t)span, hipMemcpyDeviceToHost, s));
+                } else {
+                    for (int q = q0; q < q1; ++q)
+                        if (!lists[q].empty())
+                            HIP_TRY(hipMemcpyAsync(lists[q].data(),
+                                                   ix->sbd_tmp.as<unsigned long long>() + segs[q - q0],
+                                                   8 * lists[q].size(), hipMemcpyDeviceToHost, s));
+                }
+                HIP_TRY(hipStreamSynchronize(s));
+                if (one_copy)
+                    for (int q = q0; q < q1; ++q)
+                        if (!lists[q].empty())
+                            std::memcpy(lists[q].data(), sorted.data() + segs[q - q0], 8 * lists[q].size());
+                q0 = q1;
+            }
+            ix->sbd_ids_list_ids = total;
+            ix->sbd_ids_hnsw_q = (uint64_t)nh;
+        }
+        ix->sbd_ids_legacy_q = legacy.size();
+        ix->sbd_ids_list_q = (uint64_t)nq - legacy.size();
+    }
+    std::vector<char> is_legacy(nq, 0);
+    for (int q : legacy) is_legacy[q] = 1;
+    for (int q = 0; q < nq; ++q) {
+        if (is_legacy[q]) continue;
+        const int i = hslot[q];
+        out_n[q] = sbd_emit(i >= 0 ? r1_ids.data() + (size_t)i * 100 : nullptr,
+                            i >= 0 ? r1_d.data() + (size_t)i * 100 : nullptr, i >= 0 ? r1_n[i] : 0, targets[q],
+                            max_limit, lists[q], ix->cfg.id_base, out_ids + (size_t)q * out_cap,
+                            out_dists + (size_t)q * out_cap, out_cap);
+    }
+    // the per-query path, over a bitmap row built for the query alone
+    const uint64_t nbits = std::max<uint64_t>(N, 1);
+    std::vector<uint64_t> row;
+    for (int q : legacy) {
+        row.assign((nbits + 63) / 64, 0);
+        for (uint64_t i = allow_offsets[q]; i < allow_offsets[q + 1] && allow_ids[i] < N; ++i)
+            row[allow_ids[i] >> 6] |= 1ull << (allow_ids[i] & 63);
+        int rc = wv_search_by_vector_distance(ix, queries + (size_t)q * ix->dim, targets[q], max_limit, row.data(), nbits,
+                                              out_cap ? out_ids + (size_t)q * out_cap : nullptr,
+                                              out_cap ? out_dists + (size_t)q * out_cap : nullptr, out_cap, out_n + q);
+        if (rc) return rc;
+    }
+    return WV_OK;
+}
+
+int wv_last_sbd_ids_stats(wv_index* ix, uint64_t* list_queries, uint64_t* list_ids, uint64_t* hnsw_round1_queries,
+                          uint64_t* legacy_queries) {
+    if (check(ix)) return fail(WV_EINVAL, "wv_last_sbd_ids_stats: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (list_queries) *list_queries = ix->sbd_ids_list_q;
+    if (list_ids) *list_ids = ix->sbd_ids_list_ids;
+    if (hnsw_round1_queries) *hnsw_round1_queries = ix->sbd_ids_hnsw_q;
+    if (legacy_queries) *legacy_queries = ix->sbd_ids_legacy_q;
     return WV_OK;
 }
 

@@ -16,8 +16,10 @@
 // list crosses as a bitmap or as ascending ids (the AllowList's Slice(),
 // helpers/allow_list.go:19-118); a group whose requests all carry the same
 // list sends it once (shared), a group of id lists that differ is sent as ids
-// (wv_search_batch_ids: the device walks only the listed rows), and any other
-// filtered group writes each request's list into the batch's bitmap rows.
+// (wv_search_batch_ids, or wv_search_by_vector_distance_batch_ids for a group
+// of distance searches: the device walks only the listed rows), and any other
+// filtered group -- one that mixes id lists with bitmaps, and every group of a
+// multi-GPU batcher -- writes each request's list into the batch's bitmap rows.
 //
 // Dispatch is latency-first ("natural batching"): one batch runs on the device
 // at a time, and a free worker takes EVERY request queued meanwhile the moment
@@ -176,6 +178,20 @@ struct wv_batcher {
         }
     }
 
+    // a distance group's targets and its outputs of the largest out_cap
+    static void size_dist(Staging& s) {
+        const int n = (int)s.g.size();
+        s.cap = 0;
+        s.tg.resize(n);
+        for (int i = 0; i < n; ++i) {
+            s.cap = std::max(s.cap, s.g[i]->out_cap);
+            s.tg[i] = s.g[i]->target;
+        }
+        s.ids.resize((size_t)n * std::max<int64_t>(s.cap, 1));
+        s.ds.resize((size_t)n * std::max<int64_t>(s.cap, 1));
+        s.cnt64.resize(n);
+    }
+
     // one (k, filtered) group on the device; returns the call's status
     int run_group(Staging& s) {
         const int n = (int)s.g.size();
@@ -192,7 +208,7 @@ struct wv_batcher {
             // only the listed rows (flat_search.go:24-58) and no bitmap row
             // is filled here.  (The ThreadSanitizer build's CPU index has no
             // such entry point.)
-            bool all_ids = send_ids && !shared && !grp && !s.g[0]->dist;
+            bool all_ids = send_ids && !shared && !grp;
             for (int i = 0; i < n && all_ids; ++i) all_ids = s.g[i]->allow == nullptr;
             if (all_ids) {
                 s.offs.assign((size_t)n + 1, 0);
@@ -201,6 +217,12 @@ struct wv_batcher {
                 for (int i = 0; i < n; ++i)
                     if (s.g[i]->n_ids)
                         std::memcpy(s.lists.data() + s.offs[i], s.g[i]->allow_ids, s.g[i]->n_ids * 8);
+                if (s.g[0]->dist) {
+                    size_dist(s);
+                    return wv_search_by_vector_distance_batch_ids(ix, s.q.data(), n, s.tg.data(), s.g[0]->max_limit,
+                                                                  s.lists.data(), s.offs.data(), s.ids.data(),
+                                                                  s.ds.data(), s.cap, s.cnt64.data());
+                }
                 s.ids.resize((size_t)n * k);
                 s.ds.resize((size_t)n * k);
                 s.cnt.resize(n);
@@ -218,15 +240,7 @@ struct wv_batcher {
         const uint64_t* bits = filtered ? s.bits.data() : nullptr;
         if (s.g[0]->dist) {
             // one batched SearchByVectorDistance (same maxLimit in a group)
-            s.cap = 0;
-            s.tg.resize(n);
-            for (int i = 0; i < n; ++i) {
-                s.cap = std::max(s.cap, s.g[i]->out_cap);
-                s.tg[i] = s.g[i]->target;
-            }
-            s.ids.resize((size_t)n * std::max<int64_t>(s.cap, 1));
-            s.ds.resize((size_t)n * std::max<int64_t>(s.cap, 1));
-            s.cnt64.resize(n);
+            size_dist(s);
             if (grp)
                 return wv_group_search_by_vector_distance_batch(grp, s.q.data(), n, s.tg.data(), s.g[0]->max_limit,
                                                                 bits, nbits, stride, s.ids.data(), s.ds.data(), s.cap,

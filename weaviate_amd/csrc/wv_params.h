@@ -407,6 +407,27 @@ struct SbdParams {
     unsigned int* cnt;        // [nq][3]: |Q|, A (d <= target), n (rows searchable)
 };
 
+// The threshold pass over per-query allow lists given as ids (wv_sbd.hip,
+// sbd_ids_kernel): the queries [q0, q0 + nq) of a batch, each with a segment
+// of seg_cap[i] = min(list length, cap) keys that starts at seg_beg[i]
+struct SbdIdsParams {
+    const float* X;
+    const float* Q;           // [batch][dpad] (normalized if cosine)
+    const float* target;      // [batch]
+    const uint64_t* excl;     // tombstones, nil nodes, missing rows
+    uint64_t excl_nbits;
+    const uint32_t* ids;      // every query's list, ascending within a query
+    const uint64_t* off;      // [batch + 1] into ids
+    const int* seg_beg;       // [nq] first key of query q0 + i
+    const int* seg_cap;       // [nq] its segment's length
+    uint64_t n_rows;          // ids >= n_rows are skipped
+    uint64_t chunk_len;       // ids per workgroup (a multiple of 256)
+    int q0, nq, n_chunks;
+    int D, dpad, ldx, metric;
+    unsigned long long* keys; // [sum of seg_cap]: (orderable d) << 32 | row
+    unsigned int* cnt;        // [batch][3]: |Q|, A (d <= target), n (rows searchable)
+};
+
 // Flat search over per-query id lists (wv_flat_ids.hip; flat_search.go:24-58):
 // sparse query s is batch row sel[s], its list ids[off[sel[s]] .. off[sel[s] + 1])
 struct FlatIdsParams {

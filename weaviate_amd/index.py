@@ -326,6 +326,42 @@ class GPUVectorIndex:
                                                        stride, _ptr(ids), _ptr(ds), cap, _ptr(n)))
         return [(ids[i, :min(n[i], cap)], ds[i, :min(n[i], cap)]) for i in range(nq)], n
 
+    def _id_lists(self, allow_ids, nq):
+        """One id list per query -> (flat uint64 ids, uint64 offsets [nq + 1])."""
+        lists = [np.asarray(a, dtype=np.uint64).reshape(-1) for a in allow_ids]
+        if len(lists) != nq:
+            raise WvError(1, f"allow_ids must hold one id list per query: {len(lists)} vs {nq}")
+        off = np.zeros(nq + 1, np.uint64)
+        if nq:
+            off[1:] = np.cumsum([a.size for a in lists], dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint64), dtype=np.uint64)
+        return flat, off
+
+    def search_by_vector_distance_batch_ids(self, queries, targets, allow_ids, max_limit: int = -1, cap: int = 4096):
+        """search_by_vector_distance_batch with one allow list per query given
+        as ids (a sequence of nq integer arrays, each strictly ascending): the
+        threshold pass walks only the listed rows and no bitmap is built on the
+        host (wv_search_by_vector_distance_batch_ids).  Same result."""
+        qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = qs.shape[0]
+        ts = np.ascontiguousarray(np.broadcast_to(np.asarray(targets, np.float32), (nq,)))
+        flat, off = self._id_lists(allow_ids, nq)
+        ids = np.zeros((nq, cap), np.uint64)
+        ds = np.zeros((nq, cap), np.float32)
+        n = np.zeros(nq, np.int64)
+        check(lib().wv_search_by_vector_distance_batch_ids(self._h, _ptr(qs), nq, _ptr(ts), max_limit, _ptr(flat),
+                                                           _ptr(off), _ptr(ids), _ptr(ds), cap, _ptr(n)))
+        return [(ids[i, :min(n[i], cap)], ds[i, :min(n[i], cap)]) for i in range(nq)], n
+
+    def last_sbd_ids_stats(self):
+        """The last search_by_vector_distance_batch_ids: queries answered from
+        the list pass, ids handed to it, queries whose round 1 was an HNSW
+        search, and queries that took the per-query path."""
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().wv_last_sbd_ids_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"list_queries": a.value, "list_ids": b.value, "hnsw_round1_queries": c.value,
+                "legacy_queries": d.value}
+
     def search_batch(self, queries, k: int, ef: int = 0, allow=None, mode: str = "auto"):
         """Batched search: (ids [nq,k] uint64, dists [nq,k] f32, n [nq] i32)."""
         qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
@@ -345,13 +381,7 @@ class GPUVectorIndex:
         (wv_search_batch_ids).  Same result as search_batch."""
         qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         nq = qs.shape[0]
-        lists = [np.asarray(a, dtype=np.uint64).reshape(-1) for a in allow_ids]
-        if len(lists) != nq:
-            raise WvError(1, f"allow_ids must hold one id list per query: {len(lists)} vs {nq}")
-        off = np.zeros(nq + 1, np.uint64)
-        if nq:
-            off[1:] = np.cumsum([a.size for a in lists], dtype=np.uint64)
-        flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint64), dtype=np.uint64)
+        flat, off = self._id_lists(allow_ids, nq)
         ids = np.zeros((nq, k), np.uint64)
         ds = np.zeros((nq, k), np.float32)
         n = np.zeros(nq, np.int32)
@@ -579,6 +609,23 @@ class Batcher:
         check(lib().wv_batcher_search_ids(self._h, _ptr(q), k, int(allow_ids is not None), _ptr(a), len(a), _ptr(ids),
                                           _ptr(ds), _ptr(n)))
         return ids[: n[0]], ds[: n[0]]
+
+    def search_distance_ids(self, vector, target: float, max_limit: int = -1, allow_ids=None, cap: int = 4096):
+        """SearchByVectorDistance through the batcher, the AllowList as
+        ascending ids (wv_batcher_search_distance_ids; allow_ids None = no
+        filter): (ids, dists), at most `cap` of them."""
+        q = np.ascontiguousarray(vector, dtype=np.float32)
+        if q.size != self.index.dim:
+            raise WvError(1, f"vector lengths don't match: {q.size} vs {self.index.dim}")
+        a = np.ascontiguousarray(np.zeros(0, np.uint64) if allow_ids is None else allow_ids, dtype=np.uint64)
+        ids = np.zeros(cap, np.uint64)
+        ds = np.zeros(cap, np.float32)
+        n = C.c_int64(0)
+        check(lib().wv_batcher_search_distance_ids(self._h, _ptr(q), float(target), max_limit,
+                                                   int(allow_ids is not None), _ptr(a), len(a), _ptr(ids), _ptr(ds),
+                                                   cap, C.byref(n)))
+        m = min(n.value, cap)
+        return ids[:m], ds[:m]
 
     def stats(self):
         a, b = C.c_uint64(), C.c_uint64()

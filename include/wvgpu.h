@@ -195,7 +195,12 @@ int wv_search_by_vector_distance(wv_index *ix, const float *vector, float target
  * SearchByVector where that is an HNSW search; every exact round (a flat
  * round 1, all deeper rounds) is one threshold pass + segmented sort on the
  * device, launched beside round 1 -- one device sync per batch instead of a
- * host loop of single-query searches. */
+ * host loop of single-query searches.  A PQ-compressed index runs the same
+ * flow over its codes, with the PQ distance of its searches (WV_SBD_PQ=0,
+ * read per call: the per-query rounds instead; WV_SBD_PQ_LUT=0|1: the pass
+ * evaluates rows directly / from the per-query lookup table wherever it fits,
+ * for tests and A/B runs).  A query whose within-target set outgrows
+ * WV_SBD_CAP entries takes the per-query wv_search_by_vector_distance. */
 int wv_search_by_vector_distance_batch(wv_index *ix, const float *queries, int nq, const float *target_distances,
                                        int64_t max_limit, const uint64_t *allow_bits, uint64_t allow_nbits,
                                        uint64_t allow_stride_words, uint64_t *out_ids, float *out_dists,
@@ -217,10 +222,11 @@ int wv_search_by_vector_distance_batch(wv_index *ix, const float *queries, int n
  * batch whose segments sum past 2^26 entries (WV_SBD_IDS_MAX_ENTRIES, read
  * per call; for tests) runs in consecutive chunks of queries.  The bitmap
  * rows of the HNSW round-1 queries are scattered on the device.  A query
- * whose within-target set outgrows its segment (more than WV_SBD_CAP rows),
- * a PQ-compressed index and vectors wider than 8192 floats take the
- * per-query wv_search_by_vector_distance over a bitmap row built for that
- * query alone.  Not provided: a group variant
+ * whose within-target set outgrows its segment (more than WV_SBD_CAP rows)
+ * and, on an index that is not compressed, vectors wider than 8192 floats
+ * take the per-query wv_search_by_vector_distance over a bitmap row built for
+ * that query alone.  A PQ-compressed index walks the lists over its codes
+ * (switches: wv_search_by_vector_distance_batch).  Not provided: a group variant
  * (wv_group_search_by_vector_distance_batch takes bitmaps only) and a
  * device-pointer variant. */
 int wv_search_by_vector_distance_batch_ids(wv_index *ix, const float *queries, int nq, const float *target_distances,
@@ -232,6 +238,11 @@ int wv_search_by_vector_distance_batch_ids(wv_index *ix, const float *queries, i
  * whose round 1 was an HNSW search, queries sent down the per-query path. */
 int wv_last_sbd_ids_stats(wv_index *ix, uint64_t *list_queries, uint64_t *list_ids, uint64_t *hnsw_round1_queries,
                           uint64_t *legacy_queries);
+/* The last wv_search_by_vector_distance_batch on the index (nullable
+ * outputs): queries answered from the threshold pass, queries whose round 1
+ * was an HNSW search, queries sent down the per-query path.  A null index
+ * returns WV_EINVAL. */
+int wv_last_sbd_stats(wv_index *ix, uint64_t *pass_queries, uint64_t *hnsw_round1_queries, uint64_t *legacy_queries);
 
 /* Batched search of nq queries (row-major [nq][dim]).  ef <= 0 selects
  * searchTimeEF(k).  allow_bits may be NULL, one bitmap shared by the batch

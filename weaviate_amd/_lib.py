@@ -101,6 +101,7 @@ SIGNATURES = {
     "wv_search_by_vector_distance_batch_ids": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp,
                                                          C.c_int64, _vp]),
     "wv_last_sbd_ids_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+    "wv_last_sbd_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "wv_search_batch": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp,
                                   _vp]),
     "wv_search_batch_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int,

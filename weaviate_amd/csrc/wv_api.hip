@@ -57,6 +57,8 @@ hipError_t wv_launch_sbd_ids(const wv::SbdIdsParams* p, hipStream_t s);
 hipError_t wv_sbd_ids_sort(unsigned long long* keys, unsigned long long* tmp, int n_keys, const unsigned int* cnt,
                            int q0, int nq, const int* seg_beg, const int* seg_cap, int* ends, void** scratch,
                            size_t* scratch_cap, hipStream_t s);
+hipError_t wv_launch_sbd_pq_scan(const wv::SbdPqParams* p, hipStream_t s);
+hipError_t wv_launch_sbd_pq_ids(const wv::SbdPqIdsParams* p, hipStream_t s);
 hipError_t wv_launch_pq_encode(const float* X, int ldx, const uint64_t* ids, uint64_t n_rows, const wv::PqParams* pq,
                                uint8_t* codes, hipStream_t s);
 hipError_t wv_launch_pq_scan(const wv::PqScanParams* p, hipStream_t s);
@@ -308,6 +310,7 @@ struct wv_index {
     DevBuf sbd_t, sbd_keys, sbd_tmp, sbd_cnt, sbd_off, sbd_q;
     DevBuf sbd_seg;         // (the id-list route) a chunk's segment starts, lengths and ends
     uint64_t sbd_ids_list_q = 0, sbd_ids_list_ids = 0, sbd_ids_hnsw_q = 0, sbd_ids_legacy_q = 0;   // the last call's routes
+    uint64_t sbd_pass_q = 0, sbd_hnsw_q = 0, sbd_legacy_q = 0;   // the same of the last bitmap-route batch
     void* sbd_scr = nullptr;
     size_t sbd_scr_cap = 0;
     DevBuf scan_d, scan_i, sort_d, sort_i, sort_tmp;
@@ -2963,9 +2966,24 @@ int wv_search_by_vector(wv_index* ix, const float* vector, int k, const uint64_t
 // answered by one threshold pass + segmented sort (wv_sbd.hip), launched
 // beside round 1 so the batch syncs once.  The rounds' arithmetic
 // (searchByDistParams, :552-619) then runs on the host over the counts.  A
-// query whose within-target set outgrows its list (WV_SBD_CAP, 16384) or a
-// compressed index takes the per-query path.
+// compressed index runs the same flow with the PQ distance (wv_sbd_pq.hip):
+// its exact rounds are flat searches over the codes, ordered by (dist, row).
+// A query whose within-target set outgrows its list (WV_SBD_CAP, 16384) takes
+// the per-query path.
 namespace {
+// Switches of the compressed threshold passes, read per call.  WV_SBD_PQ=0: a
+// compressed index takes the per-query path (A/B runs).  WV_SBD_PQ_LUT=0|1:
+// every workgroup evaluates rows directly / from the lookup table wherever it
+// fits; unset: the table where the workgroup's share of rows is at least ks.
+bool sbd_pq_enabled() {
+    const char* e = std::getenv("WV_SBD_PQ");
+    return !(e && e[0] == '0' && !e[1]);
+}
+int sbd_pq_lut() {
+    const char* e = std::getenv("WV_SBD_PQ_LUT");
+    return e && *e ? (std::atoi(e) ? 1 : 0) : -1;
+}
+
 // the search.go:90-158 loop over an exact sorted list (from round r0: 1 when
 // round 1 is exact too, 2 after an HNSW round 1): the end of the kept prefix
 int64_t sbd_exact_rounds(int r0, int64_t Qn, int64_t A, int64_t n, int64_t max_limit) {
@@ -3056,7 +3074,9 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
     std::vector<int> hnsw_q;   // queries whose round 1 is an HNSW search
     {
         std::lock_guard<std::mutex> g(ix->mu);
-        if (ix->pq_on) {
+        ix->sbd_pass_q = ix->sbd_hnsw_q = 0;
+        ix->sbd_legacy_q = (uint64_t)nq;
+        if (ix->pq_on && !sbd_pq_enabled()) {
             for (int q = 0; q < nq; ++q) legacy.push_back(q);
         } else {
             const int ef = search_time_ef(ix->cfg, 100);
@@ -3107,47 +3127,73 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
             // every query's threshold pass (its queries staged first: round
             // 1's search restages q_in)
             const float* dq = nullptr;
-            rc = stage_queries(ix, queries, nq, &dq, s);
-            if (rc) return rc;
-            HIP_TRY(ix->sbd_q.ensure((size_t)nq * ix->dpad * 4));
-            HIP_TRY(hipMemcpyAsync(ix->sbd_q.p, dq, (size_t)nq * ix->dpad * 4, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(ix->sbd_t.ensure((size_t)nq * 4));
-            HIP_TRY(hipMemcpyAsync(ix->sbd_t.p, targets, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(ix->sbd_keys.ensure((size_t)nq * cap * 8));
-            HIP_TRY(ix->sbd_tmp.ensure((size_t)nq * cap * 8));
-            HIP_TRY(ix->sbd_cnt.ensure((size_t)nq * 12));
-            HIP_TRY(ix->sbd_off.ensure((size_t)nq * 8));
-            HIP_TRY(hipMemsetAsync(ix->sbd_cnt.p, 0, (size_t)nq * 12, s));
-            wv::SbdParams sp{};
-            sp.X = ix->vecs.as<float>();
-            sp.Q = ix->sbd_q.as<float>();
-            sp.target = ix->sbd_t.as<float>();
-            sp.excl = ix->excl.as<uint64_t>();
-            sp.excl_nbits = ix->capacity;
-            sp.allow = dallow;
-            sp.allow_nbits = allow_nbits;
-            sp.allow_stride = allow_stride_words;
-            sp.N = ix->n_rows;
-            sp.D = ix->dim;
-            sp.ldx = ix->ldx;
-            sp.dpad = ix->dpad;
-            sp.metric = ix->metric;
-            sp.nq = nq;
-            // ~4 blocks per CU over the batch, whole 4-wave steps of 256 rows
-            const uint64_t target_blocks = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 4 / (uint64_t)nq);
-            sp.rows_per_block = std::max<uint64_t>(4096, (sp.N + target_blocks - 1) / target_blocks);
-            sp.rows_per_block = (sp.rows_per_block + 255) / 256 * 256;
-            while ((sp.N + sp.rows_per_block - 1) / sp.rows_per_block > 65535) sp.rows_per_block *= 2;
-            sp.cap = cap;
-            sp.keys = ix->sbd_keys.as<unsigned long long>();
-            sp.cnt = ix->sbd_cnt.as<unsigned int>();
-            HIP_TRY(wv_launch_sbd_scan(&sp, s));
-            HIP_TRY(wv_sbd_sort(ix->sbd_keys.as<unsigned long long>(), ix->sbd_tmp.as<unsigned long long>(),
-                                ix->sbd_cnt.as<unsigned int>(), nq, cap, ix->sbd_off.as<int>(), &ix->sbd_scr,
-                                &ix->sbd_scr_cap, s));
+            bool passed = false;
+            auto launch_pass = [&]() -> int {
+                int rc = stage_queries(ix, queries, nq, &dq, s);
+                if (rc) return rc;
+                HIP_TRY(ix->sbd_q.ensure((size_t)nq * ix->dpad * 4));
+                HIP_TRY(hipMemcpyAsync(ix->sbd_q.p, dq, (size_t)nq * ix->dpad * 4, hipMemcpyDeviceToDevice, s));
+                HIP_TRY(ix->sbd_t.ensure((size_t)nq * 4));
+                HIP_TRY(hipMemcpyAsync(ix->sbd_t.p, targets, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(ix->sbd_keys.ensure((size_t)nq * cap * 8));
+                HIP_TRY(ix->sbd_tmp.ensure((size_t)nq * cap * 8));
+                HIP_TRY(ix->sbd_cnt.ensure((size_t)nq * 12));
+                HIP_TRY(ix->sbd_off.ensure((size_t)nq * 8));
+                HIP_TRY(hipMemsetAsync(ix->sbd_cnt.p, 0, (size_t)nq * 12, s));
+                wv::SbdParams sp{};
+                sp.X = ix->vecs.as<float>();
+                sp.Q = ix->sbd_q.as<float>();
+                sp.target = ix->sbd_t.as<float>();
+                sp.excl = ix->excl.as<uint64_t>();
+                sp.excl_nbits = ix->capacity;
+                sp.allow = dallow;
+                sp.allow_nbits = allow_nbits;
+                sp.allow_stride = allow_stride_words;
+                sp.N = ix->n_rows;
+                sp.D = ix->dim;
+                sp.ldx = ix->ldx;
+                sp.dpad = ix->dpad;
+                sp.metric = ix->metric;
+                sp.nq = nq;
+                // ~4 blocks per CU over the batch, whole 4-wave steps of 256 rows
+                const uint64_t target_blocks = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 4 / (uint64_t)nq);
+                sp.rows_per_block = std::max<uint64_t>(4096, (sp.N + target_blocks - 1) / target_blocks);
+                sp.rows_per_block = (sp.rows_per_block + 255) / 256 * 256;
+                while ((sp.N + sp.rows_per_block - 1) / sp.rows_per_block > 65535) sp.rows_per_block *= 2;
+                sp.cap = cap;
+                sp.keys = ix->sbd_keys.as<unsigned long long>();
+                sp.cnt = ix->sbd_cnt.as<unsigned int>();
+                if (ix->pq_on) {
+                    wv::SbdPqParams pp{};
+                    pp.pq = pq_params(ix);
+                    pp.lut = sbd_pq_lut();
+                    // A workgroup that builds the table reads ks * D centroid
+                    // floats, 4 ks ds bytes a segment, against the m code bytes of
+                    // each row: from 4 ks ds rows a block the table's traffic is at
+                    // most the block's code traffic (and its ks * D multiply-adds
+                    // at most a quarter of its rows' m gathers), so that is the
+                    // floor where it exceeds 4096 (ks 256, ds 4: the same 4096).
+                    const uint64_t lut_floor = 4 * (uint64_t)pp.pq.ks * (uint64_t)pp.pq.ds;
+                    if (pp.lut != 0 && (uint64_t)pp.pq.m * pp.pq.ks * 4 <= (uint64_t)wv::SBD_PQ_LUT_BYTES_MAX &&
+                        sp.rows_per_block < lut_floor) {
+                        sp.rows_per_block = (lut_floor + 255) / 256 * 256;
+                        while ((sp.N + sp.rows_per_block - 1) / sp.rows_per_block > 65535) sp.rows_per_block *= 2;
+                    }
+                    pp.s = sp;
+                    HIP_TRY(wv_launch_sbd_pq_scan(&pp, s));
+                } else {
+                    HIP_TRY(wv_launch_sbd_scan(&sp, s));
+                }
+                HIP_TRY(wv_sbd_sort(ix->sbd_keys.as<unsigned long long>(), ix->sbd_tmp.as<unsigned long long>(),
+                                    ix->sbd_cnt.as<unsigned int>(), nq, cap, ix->sbd_off.as<int>(), &ix->sbd_scr,
+                                    &ix->sbd_scr_cap, s));
+                passed = true;
+                return WV_OK;
+            };
             // round 1 of the HNSW queries: their SearchByVector(limit 100)
-            if (nh) {
-                rc = stage_queries(ix, hq.data(), nh, &dq, s);
+            auto launch_r1 = [&]() -> int {
+                if (!nh) return WV_OK;
+                int rc = stage_queries(ix, hq.data(), nh, &dq, s);
                 if (rc) return rc;
                 const uint64_t* dal = dallow;
                 if (allow_bits && allow_stride_words) {
@@ -3164,8 +3210,29 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 HIP_TRY(hipMemcpyAsync(r1_ids.data(), ix->out_ids.p, (size_t)nh * 100 * 8, hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipMemcpyAsync(r1_d.data(), ix->out_d.p, (size_t)nh * 100 * 4, hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipMemcpyAsync(r1_n.data(), ix->out_n.p, (size_t)nh * 4, hipMemcpyDeviceToHost, s));
+                return WV_OK;
+            };
+            if (ix->pq_on && nq == 1 && nh == 1) {
+                // One HNSW query on a compressed index: nothing to launch the
+                // pass beside, so round 1 runs first and the pass only when
+                // round 1 lets the deepening go on (cnt stays 0 otherwise).
+                // Launched before it, the pass cost a call whose round 1 ends
+                // the deepening 0.26 ms of 10 (profiles/sbd_pq/README.md).
+                rc = launch_r1();
+                if (rc) return rc;
+                HIP_TRY(hipStreamSynchronize(s));
+                if (sbd_r1_continues(r1_d.data(), std::min<int64_t>(100, r1_n[0]), targets[0], max_limit)) {
+                    rc = launch_pass();
+                    if (rc) return rc;
+                }
+            } else {
+                rc = launch_pass();
+                if (rc) return rc;
+                rc = launch_r1();
+                if (rc) return rc;
             }
-            HIP_TRY(hipMemcpyAsync(cnt.data(), ix->sbd_cnt.p, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
+            if (passed)
+                HIP_TRY(hipMemcpyAsync(cnt.data(), ix->sbd_cnt.p, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             // the sorted lists, as far as the rounds keep them (and the caller
             // takes them)
@@ -3184,6 +3251,9 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 }
             }
             HIP_TRY(hipStreamSynchronize(s));
+            ix->sbd_legacy_q = legacy.size();
+            ix->sbd_pass_q = (uint64_t)nq - legacy.size();
+            ix->sbd_hnsw_q = (uint64_t)nh;
         }
         std::vector<int> hslot(nq, -1);
         for (int i = 0; i < nh; ++i) hslot[hnsw_q[i]] = i;
@@ -3260,9 +3330,9 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
         hipStream_t s = ix->stream;
         N = ix->n_rows;
         ix->sbd_ids_list_q = ix->sbd_ids_list_ids = ix->sbd_ids_hnsw_q = ix->sbd_ids_legacy_q = 0;
-        if (ix->pq_on || ix->dpad > wv::FLAT_IDS_DPAD_MAX) {
-            // a compressed index ranks by the PQ distance, and the kernel
-            // keeps the query row in LDS: the per-query path
+        if (ix->pq_on ? !sbd_pq_enabled() : ix->dpad > wv::FLAT_IDS_DPAD_MAX) {
+            // the uncompressed kernel keeps the query row in LDS (the
+            // compressed ones read it from memory): the per-query path
             for (int q = 0; q < nq; ++q) legacy.push_back(q);
         } else {
             int rc = refresh_bitmaps(ix);
@@ -3342,7 +3412,15 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
                     sp.metric = ix->metric;
                     sp.keys = ix->sbd_keys.as<unsigned long long>();
                     sp.cnt = ix->sbd_cnt.as<unsigned int>();
-                    HIP_TRY(wv_launch_sbd_ids(&sp, s));
+                    if (ix->pq_on) {
+                        wv::SbdPqIdsParams pp{};
+                        pp.s = sp;
+                        pp.pq = pq_params(ix);
+                        pp.lut = sbd_pq_lut();
+                        HIP_TRY(wv_launch_sbd_pq_ids(&pp, s));
+                    } else {
+                        HIP_TRY(wv_launch_sbd_ids(&sp, s));
+                    }
                     HIP_TRY(wv_sbd_ids_sort(sp.keys, ix->sbd_tmp.as<unsigned long long>(), n_keys, sp.cnt, q0, nqc,
                                             sp.seg_beg, sp.seg_cap, ix->sbd_seg.as<int>() + 2 * nqc, &ix->sbd_scr,
                                             &ix->sbd_scr_cap, s));
@@ -3461,6 +3539,15 @@ int wv_last_sbd_ids_stats(wv_index* ix, uint64_t* list_queries, uint64_t* list_i
     if (list_ids) *list_ids = ix->sbd_ids_list_ids;
     if (hnsw_round1_queries) *hnsw_round1_queries = ix->sbd_ids_hnsw_q;
     if (legacy_queries) *legacy_queries = ix->sbd_ids_legacy_q;
+    return WV_OK;
+}
+
+int wv_last_sbd_stats(wv_index* ix, uint64_t* pass_queries, uint64_t* hnsw_round1_queries, uint64_t* legacy_queries) {
+    if (check(ix)) return fail(WV_EINVAL, "wv_last_sbd_stats: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (pass_queries) *pass_queries = ix->sbd_pass_q;
+    if (hnsw_round1_queries) *hnsw_round1_queries = ix->sbd_hnsw_q;
+    if (legacy_queries) *legacy_queries = ix->sbd_legacy_q;
     return WV_OK;
 }
 

@@ -292,3 +292,11 @@ __device__ __forceinline__ int mbcnt64(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
+
+// SearchByVectorDistance's sort key (wv_sbd.hip, wv_sbd_pq.hip): the distance
+// as an orderable uint in the high word, the row in the low one
+__device__ __forceinline__ unsigned long long sbd_key(float d, uint32_t row) {
+    uint32_t u = d == 0.f ? 0u : __float_as_uint(d);   // (-0 and +0: one key)
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | row;
+}

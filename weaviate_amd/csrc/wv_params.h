@@ -467,6 +467,28 @@ struct PqScanParams {
     uint32_t* val;           // [nqc][nr] j
 };
 
+// The two threshold passes on a compressed index (wv_sbd_pq.hip): the same
+// outputs from the PQ distance (pq_dist_row's bits).  A workgroup whose share
+// of rows is at least lut_min_rows builds the query's lookup table
+// (lut[segment][centroid], m * ks floats of LDS) and adds m gathers per row;
+// any other evaluates pq_dist_row per lane.  lut_min_rows and the launch's LDS
+// are set by the launchers from `lut`: -1 = the table where it fits
+// (SBD_PQ_LUT_BYTES_MAX) and the share is at least ks rows, 0 = never, 1 =
+// wherever it fits.  X, D and ldx of the wrapped blocks are not read.
+constexpr int SBD_PQ_LUT_BYTES_MAX = 64 << 10;   // two 256-thread workgroups share a CU's 160 KiB
+struct SbdPqParams {
+    SbdParams s;
+    PqParams pq;
+    int lut;
+    uint64_t lut_min_rows;
+};
+struct SbdPqIdsParams {
+    SbdIdsParams s;
+    PqParams pq;
+    int lut;
+    uint64_t lut_min_rows;
+};
+
 // GPU graph construction: one batch of new nodes
 // [first, first + nb), inserted against the graph of the h.N nodes before it.
 struct BuildParams {

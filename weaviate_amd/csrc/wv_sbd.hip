@@ -28,14 +28,7 @@
 
 namespace wv {
 
-// SbdParams: wv_params.h
-
-
-__device__ __forceinline__ unsigned long long sbd_key(float d, uint32_t row) {
-    uint32_t u = d == 0.f ? 0u : __float_as_uint(d);   // (-0 and +0: one key)
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | row;
-}
+// SbdParams: wv_params.h; sbd_key: wv_device.h
 
 // grid (nq, row blocks), 256 threads: each wave takes 64 candidate rows a
 // step, keeps the allowed ones, computes their distances 32 at a time and

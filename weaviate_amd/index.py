@@ -362,6 +362,14 @@ class GPUVectorIndex:
         return {"list_queries": a.value, "list_ids": b.value, "hnsw_round1_queries": c.value,
                 "legacy_queries": d.value}
 
+    def last_sbd_stats(self):
+        """The last search_by_vector_distance_batch: queries answered from the
+        threshold pass, queries whose round 1 was an HNSW search, and queries
+        that took the per-query path."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().wv_last_sbd_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"pass_queries": a.value, "hnsw_round1_queries": b.value, "legacy_queries": c.value}
+
     def search_batch(self, queries, k: int, ef: int = 0, allow=None, mode: str = "auto"):
         """Batched search: (ids [nq,k] uint64, dists [nq,k] f32, n [nq] i32)."""
         qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)

@@ -121,6 +121,21 @@ int wv_index_upload_graph(wv_index *ix, uint64_t n, const int8_t *levels, const 
  * graph of all earlier batches.  The result is the index's graph (as after
  * wv_index_upload_graph, M = cfg.max_connections). */
 int wv_index_build_graph(wv_index *ix, int ef_construction, uint64_t seed, int batch_div);
+/* Insert the rows [graph n, n_rows) into the index's graph on the device, as
+ * wv_index_build_graph would have inserted them had it continued: same level
+ * draw (seed, id), same batches, the graph before them untouched except through
+ * the reverse links insert.go makes.  *inserted (nullable) = rows inserted.
+ * The graph may have been built here or uploaded; its arrays grow in place,
+ * and `upper` is re-laid when a new node is above the old top level.  Nothing
+ * to add is WV_OK with *inserted = 0.  WV_ESTATE, before anything is written
+ * (the graph and the index stay as they were): no graph; degrees other than
+ * 2 * cfg.max_connections / cfg.max_connections; a row in [graph n, n_rows)
+ * without a vector; a nil or tombstoned node below graph n (insert.go keeps
+ * deleted nodes out of its results, search.go:294, neighbor_connections.go:217,
+ * and the build search has no tombstone set: rebuild instead).  Tombstones on
+ * the new rows are no obstacle.  A device error after the checks leaves the
+ * index without a graph. */
+int wv_index_extend_graph(wv_index *ix, int ef_construction, uint64_t seed, int batch_div, uint64_t *inserted);
 /* The index's graph in the wv_index_upload_graph layout (nullable outputs). */
 int wv_index_graph_info(wv_index *ix, uint64_t *n, int *deg0, int *degU, int *max_level, uint64_t *n_upper,
                         uint64_t *entrypoint);

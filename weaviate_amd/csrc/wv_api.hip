@@ -46,6 +46,9 @@ hipError_t wv_launch_hnsw_wg(const wv::HnswParams* p, hipStream_t s);
 hipError_t wv_launch_build_search(const wv::BuildParams* b, int waves_per_block, hipStream_t s);
 hipError_t wv_launch_build_select(const wv::BuildParams* b, hipStream_t s);
 hipError_t wv_launch_build_link(const wv::BuildParams* b, hipStream_t s);
+hipError_t wv_launch_list_counts(const uint32_t* lists, uint64_t n_lists, int deg, uint32_t* counts, hipStream_t s);
+hipError_t wv_launch_upper_relay(const uint32_t* old_upper, const uint32_t* old_counts, uint64_t n_rows, int old_levels,
+                                 int new_levels, int deg, uint32_t* new_upper, uint32_t* new_counts, hipStream_t s);
 int wv_hnsw_per_wave_words(int dpad, int efc, int sc, int vc_log2, int xs_log2);
 int wv_hnsw_side_per_wave_words(int dpad, int side_rows, int vc_log2, int xs_log2);
 int wv_hnsw_reg_per_wave_words(int dpad, int vc_log2);
@@ -2034,7 +2037,7 @@ int wv_index_add(wv_index* ix, const uint64_t* ids_in, const float* rows_in, uin
     // rows -> [n][ldx] padded (normalized for cosine, insert.go:56-60), their
     // |x|^2, then scattered to their ids
     HIP_TRY(ix->stage.ensure(n * (size_t)ix->dim * 4));
-    HIP_TRY(ix->dq_tmp.ensure(n * (size_t)ix->ldx * 4 + n * 4 + n * 8));
+    HIP_TRY(ix->dq_tmp.ensure(n * (size_t)ix->ldx * 4 + (n + (n & 1)) * 4 + n * 8));   // (the ids start 8-aligned)
     float* tmp = ix->dq_tmp.as<float>();
     float* nrm = tmp + n * (size_t)ix->ldx;
     uint64_t* d_ids = reinterpret_cast<uint64_t*>(nrm + n + (n & 1));
@@ -2168,45 +2171,17 @@ static int draw_level(uint64_t seed, uint64_t id, double normalizer) {
     return t > 126 ? 126 : t;
 }
 
-int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int batch_div) {
-    if (check(ix) || ef_construction < 1 || ef_construction > wv::HNSW_EF_MAX || batch_div < 1)
-        return fail(WV_EINVAL, "wv_index_build_graph: bad argument");
-    std::lock_guard<std::mutex> guard(ix->mu);
-    HIP_TRY(hipSetDevice(ix->cfg.device));
+// insert.go:103-217 in batches (wv_hnsw.hip, "GPU graph construction"): the
+// rows [done, n) join the graph of the `done` nodes before them, whose top
+// level is `top` and entrypoint `ep`; both are updated.  The graph arrays hold
+// n nodes (the part from `done` on padded), `upper` and the upper counts have
+// the level stride ul, and the counts describe the lists.  lv: the levels of
+// the new ids only, lv[i - done].
+static int insert_batches(wv_index* ix, int ef_construction, int batch_div, uint64_t done, uint64_t n, const int8_t* lv,
+                          int ul, int& top, uint64_t& ep) {
     hipStream_t s = ix->stream;
-    const uint64_t n = ix->n_rows;
-    if (n == 0) return fail(WV_ESTATE, "wv_index_build_graph: no vectors");
-    for (uint64_t i = 0; i < n; ++i)
-        if (!(ix->has_vec[i >> 6] & (1ull << (i & 63)))) return fail(WV_ESTATE, "wv_index_build_graph: a row has no vector");
     const int M = ix->cfg.max_connections, M0 = 2 * M;
-    if (M < 2 || M0 > 256) return fail(WV_EINVAL, "wv_index_build_graph: maxConnections out of range");
-    // levels: the first node is insertInitialElement's level 0 (insert.go:67-101)
-    std::vector<int8_t> lv(n);
-    const double norm = 1.0 / std::log((double)M);
-    int maxL = 0;
-    uint64_t n_upper = 0;
-    std::vector<uint32_t> urow(n, WV_NIL);
-    for (uint64_t i = 0; i < n; ++i) {
-        lv[i] = (int8_t)(i == 0 ? 0 : draw_level(seed, i, norm));
-        maxL = std::max<int>(maxL, lv[i]);
-        if (lv[i] >= 1) urow[i] = (uint32_t)n_upper++;
-    }
-    const int ul = std::max(1, maxL);
-    HIP_TRY(ix->levels.ensure(n));
-    HIP_TRY(ix->layer0.ensure(n * (size_t)M0 * 4));
-    HIP_TRY(ix->upper_row.ensure(n * 4));
-    HIP_TRY(ix->upper.ensure(std::max<uint64_t>(1, n_upper) * ul * (size_t)M * 4));
-    HIP_TRY(ix->b_cnt0.ensure(n * 4));
-    HIP_TRY(ix->b_cntu.ensure(std::max<uint64_t>(1, n_upper) * ul * 4));
-    HIP_TRY(hipMemsetAsync(ix->levels.p, 0xFF, n, s));   // -1: not inserted yet
-    HIP_TRY(hipMemsetAsync(ix->layer0.p, 0xFF, n * (size_t)M0 * 4, s));
-    HIP_TRY(hipMemsetAsync(ix->upper.p, 0xFF, std::max<uint64_t>(1, n_upper) * ul * (size_t)M * 4, s));
-    HIP_TRY(hipMemsetAsync(ix->b_cnt0.p, 0, n * 4, s));
-    HIP_TRY(hipMemsetAsync(ix->b_cntu.p, 0, std::max<uint64_t>(1, n_upper) * ul * 4, s));
-    HIP_TRY(hipMemcpyAsync(ix->upper_row.p, urow.data(), n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ix->levels.p, lv.data(), 1, hipMemcpyHostToDevice, s));   // node 0
-    uint64_t ep = 0;
-    int top = 0;
+    const uint64_t lv0 = done;
     // per-wave search state as in run_hnsw (unfiltered layout)
     const int efc = std::max(64, (ef_construction + 63) / 64 * 64);
     const int fixed = wv_hnsw_per_wave_words(ix->dpad, efc, 0, 0, 0) - 1;
@@ -2216,7 +2191,6 @@ int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int b
     int wpb = 4;
     while (wpb > 1 && (size_t)wpb * per_wave * 4 > 160 * 1024) --wpb;
     const int bmax = 16384;
-    uint64_t done = 1;
     // WV_BUILD_TRACE=1 (diagnostic): per-phase device times (events) summed
     // over intervals of 64 batches, printed to stderr with the host time
     const bool trace = std::getenv("WV_BUILD_TRACE") != nullptr;
@@ -2229,7 +2203,8 @@ int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int b
     while (done < n) {
         const int nb = (int)std::min<uint64_t>(n - done, std::max<uint64_t>(1, std::min<uint64_t>(bmax, done / batch_div)));
         int lb = 1;
-        for (int i = 0; i < nb; ++i) lb = std::max(lb, lv[done + i] + 1);
+        const int8_t* blv = lv + (done - lv0);   // the batch's levels
+        for (int i = 0; i < nb; ++i) lb = std::max(lb, blv[i] + 1);
         HIP_TRY(ix->b_tgt.ensure(nb));
         HIP_TRY(ix->b_ci.ensure((size_t)nb * lb * ef_construction * 4));
         HIP_TRY(ix->b_cd.ensure((size_t)nb * lb * ef_construction * 4));
@@ -2243,7 +2218,7 @@ int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int b
         HIP_TRY(ix->b_ul.ensure(nreq * 4));
         HIP_TRY(ix->b_uo.ensure(nreq * 4));
         HIP_TRY(ix->b_nr.ensure(8));
-        HIP_TRY(hipMemcpyAsync(ix->b_tgt.p, lv.data() + done, nb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ix->b_tgt.p, blv, nb, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(ix->b_cn.p, 0, (size_t)nb * lb * 4, s));
         wv::BuildParams b{};
         wv::HnswParams& h = b.h;
@@ -2343,14 +2318,58 @@ int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int b
             }
         }
         // the batch is in the graph: its levels make it reachable for the next one
-        HIP_TRY(hipMemcpyAsync(ix->levels.as<int8_t>() + done, lv.data() + done, nb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ix->levels.as<int8_t>() + done, blv, nb, hipMemcpyHostToDevice, s));
         for (int i = 0; i < nb; ++i)   // insert.go:202-213: a higher node becomes the entrypoint
-            if (lv[done + i] > top) { top = lv[done + i]; ep = done + i; }
+            if (blv[i] > top) { top = blv[i]; ep = done + i; }
         done += nb;
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (trace)
         for (auto& e : tev) HIP_TRY(hipEventDestroy(e));
+    return WV_OK;
+}
+
+int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int batch_div) {
+    if (check(ix) || ef_construction < 1 || ef_construction > wv::HNSW_EF_MAX || batch_div < 1)
+        return fail(WV_EINVAL, "wv_index_build_graph: bad argument");
+    std::lock_guard<std::mutex> guard(ix->mu);
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    hipStream_t s = ix->stream;
+    const uint64_t n = ix->n_rows;
+    if (n == 0) return fail(WV_ESTATE, "wv_index_build_graph: no vectors");
+    for (uint64_t i = 0; i < n; ++i)
+        if (!(ix->has_vec[i >> 6] & (1ull << (i & 63)))) return fail(WV_ESTATE, "wv_index_build_graph: a row has no vector");
+    const int M = ix->cfg.max_connections, M0 = 2 * M;
+    if (M < 2 || M0 > 256) return fail(WV_EINVAL, "wv_index_build_graph: maxConnections out of range");
+    // levels: the first node is insertInitialElement's level 0 (insert.go:67-101)
+    std::vector<int8_t> lv(n);
+    const double norm = 1.0 / std::log((double)M);
+    int maxL = 0;
+    uint64_t n_upper = 0;
+    std::vector<uint32_t> urow(n, WV_NIL);
+    for (uint64_t i = 0; i < n; ++i) {
+        lv[i] = (int8_t)(i == 0 ? 0 : draw_level(seed, i, norm));
+        maxL = std::max<int>(maxL, lv[i]);
+        if (lv[i] >= 1) urow[i] = (uint32_t)n_upper++;
+    }
+    const int ul = std::max(1, maxL);
+    HIP_TRY(ix->levels.ensure(n));
+    HIP_TRY(ix->layer0.ensure(n * (size_t)M0 * 4));
+    HIP_TRY(ix->upper_row.ensure(n * 4));
+    HIP_TRY(ix->upper.ensure(std::max<uint64_t>(1, n_upper) * ul * (size_t)M * 4));
+    HIP_TRY(ix->b_cnt0.ensure(n * 4));
+    HIP_TRY(ix->b_cntu.ensure(std::max<uint64_t>(1, n_upper) * ul * 4));
+    HIP_TRY(hipMemsetAsync(ix->levels.p, 0xFF, n, s));   // -1: not inserted yet
+    HIP_TRY(hipMemsetAsync(ix->layer0.p, 0xFF, n * (size_t)M0 * 4, s));
+    HIP_TRY(hipMemsetAsync(ix->upper.p, 0xFF, std::max<uint64_t>(1, n_upper) * ul * (size_t)M * 4, s));
+    HIP_TRY(hipMemsetAsync(ix->b_cnt0.p, 0, n * 4, s));
+    HIP_TRY(hipMemsetAsync(ix->b_cntu.p, 0, std::max<uint64_t>(1, n_upper) * ul * 4, s));
+    HIP_TRY(hipMemcpyAsync(ix->upper_row.p, urow.data(), n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ix->levels.p, lv.data(), 1, hipMemcpyHostToDevice, s));   // node 0
+    uint64_t ep = 0;
+    int top = 0;
+    int rc = insert_batches(ix, ef_construction, batch_div, 1, n, lv.data() + 1, ul, top, ep);
+    if (rc) return rc;
     ix->nil_host.assign(ix->bm_words, ~0ull);
     for (uint64_t i = 0; i < lv.size(); ++i)
         if (lv[i] >= 0) ix->nil_host[i >> 6] &= ~(1ull << (i & 63));
@@ -2364,6 +2383,155 @@ int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int b
     ix->any_nil = false;
     for (uint64_t i = 0; i < n; ++i) ix->pending_host[i >> 6] &= ~(1ull << (i & 63));
     ix->bitmaps_dirty = true;
+    return WV_OK;
+}
+
+// A graph array at new_bytes: the first old_bytes kept, the rest filled with
+// `pad` (regrow zero-fills and skips unallocated buffers; the graph's arrays
+// pad with 0xFF).  A buffer that moves is freed once the device is idle: a
+// search queued on a caller's stream may still read it.
+static hipError_t grow_padded(DevBuf& b, size_t old_bytes, size_t new_bytes, int pad, hipStream_t s) {
+    if (new_bytes <= old_bytes) return hipSuccess;
+    if (new_bytes <= b.cap) return hipMemsetAsync(static_cast<char*>(b.p) + old_bytes, pad, new_bytes - old_bytes, s);
+    size_t want = std::max<size_t>(new_bytes, 256);
+    if (b.cap) want = std::max(want, std::min(b.cap + b.cap / 2, new_bytes + ((size_t)256 << 20)));
+    void* np = nullptr;
+    hipError_t e = hipMalloc(&np, want);
+    if (e != hipSuccess) return e;
+    old_bytes = std::min(old_bytes, b.cap);
+    if (old_bytes) e = hipMemcpyAsync(np, b.p, old_bytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(static_cast<char*>(np) + old_bytes, pad, new_bytes - old_bytes, s);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(np); return e; }
+    if (b.p) (void)hipFree(b.p);
+    b.p = np;
+    b.cap = want;
+    return hipSuccess;
+}
+
+int wv_index_extend_graph(wv_index* ix, int ef_construction, uint64_t seed, int batch_div, uint64_t* inserted) {
+    if (inserted) *inserted = 0;
+    if (ef_construction < 1 || ef_construction > wv::HNSW_EF_MAX)
+        return fail(WV_EINVAL, "wv_index_extend_graph: ef_construction outside 1.." + std::to_string(wv::HNSW_EF_MAX));
+    if (batch_div < 1) return fail(WV_EINVAL, "wv_index_extend_graph: batch_div < 1");
+    if (check(ix)) return WV_EINVAL;
+    std::lock_guard<std::mutex> guard(ix->mu);
+    if (!ix->has_graph || ix->gn == 0) return fail(WV_ESTATE, "wv_index_extend_graph: the index has no graph");
+    const uint64_t gn = ix->gn, n = ix->n_rows;
+    if (n <= gn) return WV_OK;   // nothing to add
+    const int M = ix->cfg.max_connections, M0 = 2 * M;
+    if (M < 2 || M0 > 256) return fail(WV_ESTATE, "wv_index_extend_graph: maxConnections out of range");
+    if (ix->deg0 != M0 || ix->degU != M)
+        return fail(WV_ESTATE, "wv_index_extend_graph: the graph's degrees (" + std::to_string(ix->deg0) + ", " +
+                                   std::to_string(ix->degU) + ") are not 2 x maxConnections and maxConnections (" +
+                                   std::to_string(M0) + ", " + std::to_string(M) + ")");
+    // The build search passes no tombstone set, and insert.go keeps deleted
+    // nodes out of its results (search.go:294, neighbor_connections.go:217):
+    // over a graph that holds nil or tombstoned nodes the caller rebuilds.
+    for (uint64_t i = 0; i < gn; ++i) {
+        const uint64_t bit = 1ull << (i & 63);
+        if (ix->nil_host[i >> 6] & bit)
+            return fail(WV_ESTATE, "wv_index_extend_graph: graph node " + std::to_string(i) + " is nil");
+        if (ix->tomb_host[i >> 6] & bit)
+            return fail(WV_ESTATE, "wv_index_extend_graph: graph node " + std::to_string(i) + " has a tombstone");
+    }
+    for (uint64_t i = gn; i < n; ++i)
+        if (!(ix->has_vec[i >> 6] & (1ull << (i & 63))))
+            return fail(WV_ESTATE, "wv_index_extend_graph: row " + std::to_string(i) + " has no vector");
+    // levels and `upper` rows of the new ids (the draw of wv_index_build_graph)
+    const uint64_t k = n - gn;
+    std::vector<int8_t> lv(k);
+    std::vector<uint32_t> urow(k, WV_NIL);
+    const double norm = 1.0 / std::log((double)M);
+    int maxL = ix->max_level;
+    uint64_t n_upper = ix->n_upper;
+    for (uint64_t i = 0; i < k; ++i) {
+        lv[i] = (int8_t)draw_level(seed, gn + i, norm);
+        maxL = std::max<int>(maxL, lv[i]);
+        if (lv[i] >= 1) urow[i] = (uint32_t)n_upper++;
+    }
+    const int ul_old = std::max(1, ix->max_level), ul = std::max(1, maxL);
+    const uint64_t nu_old = ix->n_upper;
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    hipStream_t s = ix->stream;
+    HIP_TRY(hipStreamSynchronize(s));
+    // WV_BUILD_TRACE=1 (diagnostic): the preparation's steps, each waited for
+    const bool trace = std::getenv("WV_BUILD_TRACE") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    double t_step[3] = {0, 0, 0};   // growth, counts, re-layout
+    auto step_done = [&](int i) -> hipError_t {
+        if (!trace) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        t_step[i] += std::chrono::duration<double, std::milli>(now - t0).count();
+        t0 = now;
+        return e;
+    };
+    // the per-node arrays at n nodes: the new part not inserted yet (-1), empty
+    HIP_TRY(grow_padded(ix->levels, gn, n, 0xFF, s));
+    HIP_TRY(grow_padded(ix->layer0, gn * (size_t)M0 * 4, n * (size_t)M0 * 4, 0xFF, s));
+    HIP_TRY(grow_padded(ix->upper_row, gn * 4, n * 4, 0xFF, s));
+    HIP_TRY(hipMemcpyAsync(ix->upper_row.as<uint32_t>() + gn, urow.data(), k * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(step_done(0));
+    // neighbour counts, read off the lists (none are kept between calls)
+    HIP_TRY(ix->b_cnt0.ensure(n * 4));
+    HIP_TRY(hipMemsetAsync(ix->b_cnt0.p, 0, n * 4, s));
+    HIP_TRY(wv_launch_list_counts(ix->layer0.as<uint32_t>(), gn, M0, ix->b_cnt0.as<uint32_t>(), s));
+    const size_t cu_words = std::max<uint64_t>(1, n_upper) * (size_t)ul;
+    if (ul != ul_old || n_upper != nu_old) {
+        // `upper` re-laid at [n_upper][ul][M], its counts with it
+        HIP_TRY(ix->b_tmp.ensure(std::max<uint64_t>(1, nu_old) * (size_t)ul_old * 4));
+        HIP_TRY(wv_launch_list_counts(ix->upper.as<uint32_t>(), nu_old * (uint64_t)ul_old, M, ix->b_tmp.as<uint32_t>(),
+                                      s));
+        HIP_TRY(step_done(1));
+        DevBuf up;
+        HIP_TRY(up.ensure(cu_words * M * 4));
+        hipError_t e = ix->b_cntu.ensure(cu_words * 4);
+        if (e == hipSuccess) e = hipMemsetAsync(up.p, 0xFF, cu_words * M * 4, s);
+        if (e == hipSuccess) e = hipMemsetAsync(ix->b_cntu.p, 0, cu_words * 4, s);
+        if (e == hipSuccess)
+            e = wv_launch_upper_relay(ix->upper.as<uint32_t>(), ix->b_tmp.as<uint32_t>(), nu_old, ul_old, ul, M,
+                                      up.as<uint32_t>(), ix->b_cntu.as<uint32_t>(), s);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            up.release();
+            HIP_TRY(e);
+        }
+        std::swap(ix->upper, up);
+        up.release();
+        HIP_TRY(step_done(2));
+    } else {
+        HIP_TRY(ix->b_cntu.ensure(cu_words * 4));
+        HIP_TRY(hipMemsetAsync(ix->b_cntu.p, 0, cu_words * 4, s));
+        HIP_TRY(wv_launch_list_counts(ix->upper.as<uint32_t>(), nu_old * (uint64_t)ul, M, ix->b_cntu.as<uint32_t>(), s));
+        HIP_TRY(step_done(1));
+    }
+    if (trace)
+        std::fprintf(stderr,
+                     "[extend] %llu nodes + %llu rows, upper %llu x %d -> %llu x %d: grow %.2f ms, counts %.2f ms, "
+                     "re-layout %.2f ms\n",
+                     (unsigned long long)gn, (unsigned long long)k, (unsigned long long)nu_old, ul_old,
+                     (unsigned long long)n_upper, ul, t_step[0], t_step[1], t_step[2]);
+    // from here on `upper` has the stride of the graph to come: a failure
+    // below leaves the index without a graph (its rows are still served exactly)
+    int top = ix->max_level;
+    uint64_t ep = ix->entrypoint;
+    int rc = insert_batches(ix, ef_construction, batch_div, gn, n, lv.data(), ul, top, ep);
+    if (rc) {
+        ix->has_graph = false;
+        ix->bitmaps_dirty = true;
+        return rc;
+    }
+    for (uint64_t i = gn; i < n; ++i) {
+        ix->nil_host[i >> 6] &= ~(1ull << (i & 63));
+        ix->pending_host[i >> 6] &= ~(1ull << (i & 63));
+    }
+    ix->gn = n;
+    ix->max_level = top;
+    ix->n_upper = n_upper;
+    ix->entrypoint = ep;
+    ix->bitmaps_dirty = true;
+    if (inserted) *inserted = k;
     return WV_OK;
 }
 

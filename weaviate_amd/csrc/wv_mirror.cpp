@@ -848,7 +848,14 @@ int wv_mirror_compact(wv_mirror* m) {
     }
     std::unique_lock<FairRW> l(m->mu);
     if (!m->live() || !m->ix) return err(WV_ESTALE, "wv_mirror: stale");
-    int rc = wv_index_build_graph(m->ix, m->opt.ef_construction, m->opt.build_seed, 32);
+    // the rows added since join the graph (the search lock is held for the
+    // rows added, not for all of them); where only a rebuild applies -- no
+    // graph yet, deleted nodes in it, other degrees -- the whole graph is built
+    int rc = WV_ESTATE;
+#ifndef WV_TSAN_BUILD   // (the ThreadSanitizer build's CPU index has no such entry point)
+    rc = wv_index_extend_graph(m->ix, m->opt.ef_construction, m->opt.build_seed, 32, nullptr);
+#endif
+    if (rc == WV_ESTATE) rc = wv_index_build_graph(m->ix, m->opt.ef_construction, m->opt.build_seed, 32);
     if (rc) return rc;   // e.g. holes below n_rows: the delta keeps serving exactly
     uint64_t n = 0;
     wv_index_graph_info(m->ix, &n, nullptr, nullptr, nullptr, nullptr, nullptr);

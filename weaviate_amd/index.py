@@ -170,6 +170,14 @@ class GPUVectorIndex:
         """Build the HNSW graph of the uploaded rows on the GPU (wv_index_build_graph)."""
         check(lib().wv_index_build_graph(self._h, ef_construction, seed, batch_div))
 
+    def extend_graph(self, ef_construction: int = 128, seed: int = 1, batch_div: int = 32) -> int:
+        """Insert the rows added since the graph was built or uploaded into it, on the
+        GPU (wv_index_extend_graph): the build continued, O(rows added).  Returns
+        the number of rows inserted; WvError code 4 where only a rebuild applies."""
+        k = C.c_uint64()
+        check(lib().wv_index_extend_graph(self._h, ef_construction, seed, batch_div, C.byref(k)))
+        return k.value
+
     def query_ld(self) -> int:
         """Row stride (floats) of the device query rows search_batch_device reads."""
         return lib().wv_index_query_ld(self._h)

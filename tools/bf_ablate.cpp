@@ -4,11 +4,10 @@
 #include <cstdlib>
 #include <vector>
 #include <cstring>
-#include "../weaviate_amd/csrc/wv_params.h"
+#include "../weaviate_amd/csrc/wv_launch.h"
 #ifdef WV_BF_DBG_ITERS
 extern "C" void wv_dbg_read(unsigned long long*);
 #endif
-extern "C" hipError_t wv_launch_bf_mfma(const wv::BfParams* p, hipStream_t s);
 int main(int argc, char** argv) {
     const uint64_t N = argc > 1 ? atoll(argv[1]) : 1000000;
     const int nq = argc > 2 ? atoi(argv[2]) : 10000, D = 128;

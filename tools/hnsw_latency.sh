@@ -11,13 +11,14 @@ if [ "$1" == "build" ]; then
   make -s -C $C ARCH=gfx950
   /opt/rocm/bin/hipcc $HF -fopenmp -x hip -c tools/hnsw_latency.cpp -o $B/main.o
   rm -f $B/lat_*
+  # the library's objects, but for the variant's wv_hnsw.o
+  OBJS=$(for o in $(make -s -C $C objs); do [ $o == wv_hnsw.o ] || echo $C/$o; done)
   for v in $VARIANTS; do
     name=${v%%=*}; defs=${v#*=}; defs=${defs//:/ }
     (
     if [ -z "$defs" ]; then cp $C/wv_hnsw.o $B/hnsw_$name.o; else
       /opt/rocm/bin/hipcc $HF $defs -c $C/wv_hnsw.hip -o $B/hnsw_$name.o; fi
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -fopenmp -pthread $B/main.o $B/hnsw_$name.o $C/wv_bf.o $C/wv_h16.o $C/wv_pq.o \
-        $C/wv_api.o $C/wv_batcher.o $C/wv_commitlog.o $C/wv_group.o $C/wv_mirror.o -L/opt/rocm/lib -lrccl -o $B/lat_$name
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -fopenmp -pthread $B/main.o $B/hnsw_$name.o $OBJS -L/opt/rocm/lib -lrccl -o $B/lat_$name
     ) &
   done
   wait

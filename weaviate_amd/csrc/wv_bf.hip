@@ -18,6 +18,7 @@
 //   3. wv_exact_scan_kernel + radix sort: exact reference-order distances for
 //      every id, used for flagged queries and for large k.
 #include "wv_device.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 #include "wv_topk.h"
 

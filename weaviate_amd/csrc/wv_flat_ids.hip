@@ -15,6 +15,7 @@
 // flat_ids_merge_kernel.  The path is exact from the start: no key pass, no
 // certificate.
 #include "wv_device.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 #include "wv_topk.h"
 

@@ -19,6 +19,8 @@
 
 #include <cstdint>
 
+#include "wv_launch.h"
+
 namespace wv {
 
 constexpr uint32_t GG_NIL = 0xFFFFFFFFu;

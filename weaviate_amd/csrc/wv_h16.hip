@@ -24,6 +24,7 @@
 //    H_SAMPLE-th tile, wv_api.hip) starts every list with a tail, so the rare
 //    extraction runs on hits below the seed only.
 #include "wv_device.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 #include "wv_topk.h"
 

@@ -29,6 +29,7 @@
 // set is exact.
 #include "wv_device.h"
 #include "wv_h16_dev.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 
 #include <float.h>

@@ -13,6 +13,7 @@
 // The HNSW kernel computes the same PQ distance per gathered row
 // (wv_hnsw.hip, pq_dist_row in wv_device.h).
 #include "wv_device.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 
 namespace wv {

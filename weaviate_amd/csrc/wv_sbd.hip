@@ -22,6 +22,7 @@
 // ids and reads only the listed rows, each query appending into a segment of
 // its own length.
 #include "wv_device.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 
 #include <hipcub/hipcub.hpp>

@@ -22,6 +22,7 @@
 // rows directly costs rows * D.  Otherwise (ks 65536, many segments, a list
 // chunk shorter than ks) each lane calls pq_dist_row.
 #include "wv_device.h"
+#include "wv_launch.h"
 #include "wv_params.h"
 
 namespace wv {

@@ -276,13 +276,28 @@ int wv_search_batch(wv_index *ix, const float *queries, int nq, int k, int ef, c
  * ascend, return WV_EINVAL.  Flat or HNSW is decided per query on the host
  * from the list's length (AUTO: search.go:64-79; EXACT: flat; HNSW: HNSW).  A
  * flat query is answered by the sparse kernel, which reads only the listed
- * rows (flat_search.go:24-58), unless the index is PQ-compressed, k > 256, a
- * vector is wider than 8192 floats or, in EXACT mode, the list holds an
- * eighth of the rows or more; those and the HNSW queries run as
- * wv_search_batch over bitmap rows built on the device. */
+ * rows (flat_search.go:24-58), unless k > 256, a vector of an uncompressed
+ * index is wider than 8192 floats or, in EXACT mode, the list holds an eighth
+ * of the rows or more; those and the HNSW queries run as wv_search_batch over
+ * bitmap rows built on the device.  On a PQ-compressed index the flat queries
+ * take the bitmap route too unless wv_index_set_pq_list_search is on: then the
+ * list kernel walks the listed rows' codes, with the PQ distance of the
+ * index's searches, under the same conditions (any dimension).
+ * WV_FLAT_IDS_PQ_LUT=0|1, read per call: that kernel evaluates rows directly /
+ * from the per-query lookup table wherever it fits (unset: the table where a
+ * workgroup's chunk of the list holds at least `centroids` ids); for tests and
+ * A/B runs. */
 int wv_search_batch_ids(wv_index *ix, const float *queries, int nq, int k, int ef, const uint64_t *allow_ids,
                         const uint64_t *allow_offsets /* [nq+1] */, int mode, uint64_t *out_ids, float *out_dists,
                         int32_t *out_n);
+/* Flat queries of wv_search_batch_ids on a compressed index walk their lists
+ * over the codes (on) or take the bitmap route (off, the default).  The
+ * answers are the same bits either way; the list kernel reads and sorts only
+ * the listed rows.  The setting may be made before or after compression and
+ * has no effect on an uncompressed index; a null index returns WV_EINVAL.
+ * (Off by default because the suite pins the bitmap route's counts for a
+ * compressed index; making on the library default is a follow-up.) */
+int wv_index_set_pq_list_search(wv_index *ix, int on);
 /* The last wv_search_batch_ids on the index (nullable outputs): queries answered
  * by the sparse flat kernel, ids handed to it, queries sent down the bitmap route. */
 int wv_last_sparse_stats(wv_index *ix, uint64_t *sparse_queries, uint64_t *sparse_ids, uint64_t *bitmap_queries);

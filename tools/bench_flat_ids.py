@@ -23,6 +23,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from weaviate_amd import _lib  # noqa: E402
+
+if os.environ.get("WV_LIBPATH"):   # an older build is bound as far as its symbols go
+    _probe = C.CDLL(_lib.LIBPATH)
+    for _name in [s for s in _lib.SIGNATURES if not hasattr(_probe, s)]:
+        del _lib.SIGNATURES[_name]
 import weaviate_amd as W  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes/s (spec)

@@ -108,6 +108,7 @@ SIGNATURES = {
     "wv_search_batch_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int,
                                          _vp, _vp, _vp, _vp]),
     "wv_search_batch_ids": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "wv_index_set_pq_list_search": (C.c_int, [_vp, C.c_int]),
     "wv_last_sparse_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "wv_last_sparse_time": (C.c_int, [_vp, _f32p]),
     "wv_index_query_ld": (C.c_int, [_vp]),

@@ -723,6 +723,13 @@ int wv_index_set_compressed(wv_index* ix, int on) {
     return WV_OK;
 }
 
+int wv_index_set_pq_list_search(wv_index* ix, int on) {
+    if (!ix) return fail(WV_EINVAL, "wv_index_set_pq_list_search: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->pq_list_search = on != 0;
+    return WV_OK;
+}
+
 int wv_search_time_ef(const wv_index* ix, int k) { return ix ? search_time_ef(ix->cfg, k) : -1; }
 int wv_config_search_time_ef(const wv_config* cfg, int k) { return cfg ? search_time_ef(*cfg, k) : -1; }
 

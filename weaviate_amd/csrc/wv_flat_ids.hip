@@ -14,9 +14,15 @@
 // smallest of both).  The waves merge through LDS, the chunks of a query in
 // flat_ids_merge_kernel.  The path is exact from the start: no key pass, no
 // certificate.
+//
+// On a compressed index (flat_ids_pq_kernel) the walk, the selection and the
+// merges are the same; the distance is the PQ distance of the id's codes, one
+// row per lane, from the query's lookup table in LDS (wv_pq_lut.h) or from
+// pq_dist_row -- the same bits.
 #include "wv_device.h"
 #include "wv_launch.h"
 #include "wv_params.h"
+#include "wv_pq_lut.h"
 #include "wv_topk.h"
 
 namespace wv {
@@ -92,8 +98,9 @@ __device__ __forceinline__ uint64_t fi_kth(const uint64_t (&top)[4], int k) {
     return fi_shfl(v, (k - 1) & 63);
 }
 
-template <int METRIC>
-__device__ __forceinline__ void fi_write(const FlatIdsParams& p, const uint64_t (&top)[4], int q, int lane) {
+// (P: FlatIdsParams or FlatIdsPqParams -- the same output fields)
+template <int METRIC, class P>
+__device__ __forceinline__ void fi_write(const P& p, const uint64_t (&top)[4], int q, int lane) {
     int n = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -112,6 +119,35 @@ __device__ __forceinline__ void fi_write(const FlatIdsParams& p, const uint64_t 
         n += __popcll(__ballot(has));
     }
     if (lane == 0) p.out_n[q] = n;
+}
+
+// The end of a workgroup's walk: each wave's last staged keys flushed, the
+// waves merged through their stages, and wave 0 writes the query's output rows
+// (one chunk) or the chunk's sorted keys for flat_ids_merge_kernel.
+template <int METRIC, class P>
+__device__ __forceinline__ void fi_finish(const P& p, uint64_t (&top)[4], uint64_t* stage_all, uint64_t* stage, int cnt,
+                                          int s, int chunk, int q, int lane, int wave) {
+    if (cnt) fi_flush(top, stage, cnt, lane);
+    fi_wave_sync();
+    // the waves of the workgroup: each leaves its sorted keys in its stage
+#pragma unroll
+    for (int j = 0; j < 4; ++j) stage[64 * j + lane] = top[j];
+    __syncthreads();
+    if (wave != 0) return;
+    for (int w = 1; w < 4; ++w) {
+        uint64_t od[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) od[j] = stage_all[w * FI_STAGE + 255 - (64 * j + lane)];
+        fi_merge(top, od, lane);
+    }
+    if (p.n_chunks == 1) {
+        fi_write<METRIC>(p, top, q, lane);
+    } else {
+        unsigned long long* out = p.part + ((size_t)s * p.n_chunks + chunk) * p.k;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (64 * j + lane < p.k) out[64 * j + lane] = top[j];
+    }
 }
 
 // grid (ns, n_chunks), 256 threads; dynamic LDS: stage | ids | dists | query
@@ -167,27 +203,59 @@ __global__ __launch_bounds__(256) void flat_ids_kernel(FlatIdsParams p) {
             fi_wave_sync();
         }
     }
-    if (cnt) fi_flush(top, stage, cnt, lane);
-    fi_wave_sync();
-    // the waves of the workgroup: each leaves its sorted keys in its stage
-#pragma unroll
-    for (int j = 0; j < 4; ++j) stage[64 * j + lane] = top[j];
-    __syncthreads();
-    if (wave != 0) return;
-    for (int w = 1; w < 4; ++w) {
-        uint64_t od[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) od[j] = stage_all[w * FI_STAGE + 255 - (64 * j + lane)];
-        fi_merge(top, od, lane);
+    fi_finish<METRIC>(p, top, stage_all, stage, cnt, s, chunk, q, lane, wave);
+}
+
+// The same walk on a compressed index: grid (ns, n_chunks), 256 threads;
+// dynamic LDS: stage | lookup table.  Each lane evaluates its own id's row from
+// the codes -- no compaction into slots -- by the workgroup's table where the
+// chunk holds at least lut_min_rows ids (the whole workgroup agrees), else by
+// pq_dist_row on the query row in memory: the same bits either way.
+template <int METRIC>
+__global__ __launch_bounds__(256) void flat_ids_pq_kernel(FlatIdsPqParams p) {
+    extern __shared__ __attribute__((aligned(16))) char fi_smem[];
+    uint64_t* stage_all = reinterpret_cast<uint64_t*>(fi_smem);          // [4][FI_STAGE]
+    float* lut = reinterpret_cast<float*>(fi_smem + 4 * FI_STAGE * 8);   // [m][ks] (when built)
+    const int s = blockIdx.x, chunk = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = p.sel[s];
+    uint64_t* stage = stage_all + wave * FI_STAGE;
+    const uint64_t l_end = p.off[q + 1];
+    uint64_t beg = p.off[q] + (uint64_t)chunk * p.chunk_len;
+    if (beg > l_end) beg = l_end;
+    const uint64_t end = l_end - beg > p.chunk_len ? beg + p.chunk_len : l_end;
+    const float* qrow = p.Q + (uint64_t)q * p.dpad;
+    const bool use_lut = end > beg && end - beg >= p.lut_min_rows;
+    if (use_lut) pq_lut_build<METRIC>(lut, qrow, p.pq);
+
+    uint64_t top[4] = {FI_EMPTY, FI_EMPTY, FI_EMPTY, FI_EMPTY};
+    uint64_t kth = FI_EMPTY;
+    int cnt = 0;
+    for (uint64_t i0 = beg + (uint64_t)FI_STEP * wave; i0 < end; i0 += 4 * FI_STEP) {
+        const uint64_t i = i0 + lane;
+        uint32_t id = 0;
+        bool ok = false;
+        if (i < end) {
+            id = p.ids[i];
+            ok = id < p.n_rows && !bit_test(p.excl, p.excl_nbits, id);
+        }
+        if (__ballot(ok) == 0) continue;
+        float d = 0.f;
+        if (ok) d = use_lut ? pq_lut_dist<METRIC>(lut, p.pq, id) : pq_dist_row<METRIC>(qrow, p.pq, id);
+        const uint64_t key = ok ? fin_key(d, id) : FI_EMPTY;
+        const bool adm = key < kth;
+        const uint64_t am = __ballot(adm);
+        if (adm) stage[cnt + mbcnt64(am)] = key;
+        cnt += __popcll(am);
+        fi_wave_sync();
+        if (cnt > FI_STAGE - FI_STEP) {
+            fi_flush(top, stage, cnt, lane);
+            cnt = 0;
+            kth = fi_kth(top, p.k);
+            fi_wave_sync();
+        }
     }
-    if (p.n_chunks == 1) {
-        fi_write<METRIC>(p, top, q, lane);
-    } else {
-        unsigned long long* out = p.part + ((size_t)s * p.n_chunks + chunk) * p.k;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (64 * j + lane < p.k) out[64 * j + lane] = top[j];
-    }
+    fi_finish<METRIC>(p, top, stage_all, stage, cnt, s, chunk, q, lane, wave);
 }
 
 // one wave per query: its chunks' sorted keys merged, then the output rows
@@ -242,6 +310,39 @@ hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s) {
         hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_DOT>, dim3(p->ns), dim3(64), 0, s, *p);
     else
         hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_L2>, dim3(p->ns), dim3(64), 0, s, *p);
+    return hipGetLastError();
+}
+
+hipError_t wv_launch_flat_ids_pq(const wv::FlatIdsPqParams* p, hipStream_t s) {
+    if (p->ns == 0) return hipSuccess;
+    if (p->k < 1 || p->k > 256 || p->n_chunks < 1 || p->n_chunks > 65535 || p->chunk_len == 0 ||
+        p->chunk_len % 256 || (p->n_chunks > 1 && !p->part) || !wv::pq_ok(p->pq))
+        return hipErrorInvalidValue;
+    wv::FlatIdsPqParams pp = *p;
+    // stage 8 KiB + a table of at most 64 KiB: two workgroups in a CU's 160 KiB
+    const size_t lds = 4 * wv::FI_STAGE * 8 + wv::lut_plan(pp.pq, pp.lut, &pp.lut_min_rows);
+    const dim3 grid((unsigned)pp.ns, (unsigned)pp.n_chunks);
+    if (pp.metric == WV_METRIC_L2) hipLaunchKernelGGL(wv::flat_ids_pq_kernel<WV_METRIC_L2>, grid, dim3(256), lds, s, pp);
+    else if (pp.metric == WV_METRIC_DOT) hipLaunchKernelGGL(wv::flat_ids_pq_kernel<WV_METRIC_DOT>, grid, dim3(256), lds, s, pp);
+    else hipLaunchKernelGGL(wv::flat_ids_pq_kernel<WV_METRIC_COSINE>, grid, dim3(256), lds, s, pp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || pp.n_chunks == 1) return e;
+    // the chunks' keys merge as the raw kernel's do: the fields flat_ids_merge_kernel reads
+    wv::FlatIdsParams mp{};
+    mp.sel = pp.sel;
+    mp.id_base = pp.id_base;
+    mp.part = pp.part;
+    mp.ns = pp.ns;
+    mp.n_chunks = pp.n_chunks;
+    mp.metric = pp.metric;
+    mp.k = pp.k;
+    mp.out_ids = pp.out_ids;
+    mp.out_d = pp.out_d;
+    mp.out_n = pp.out_n;
+    if (mp.metric == WV_METRIC_DOT)
+        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_DOT>, dim3(mp.ns), dim3(64), 0, s, mp);
+    else
+        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_L2>, dim3(mp.ns), dim3(64), 0, s, mp);
     return hipGetLastError();
 }
 

@@ -149,6 +149,7 @@ struct wv_index {
     // per segment, rows padded to whole words; has_code marks rows encoded.
     int pq_m = 0, pq_ks = 0, pq_ds = 0, pq_encoder = 0;
     bool pq_set = false, pq_on = false, pq_use_bits = false;
+    bool pq_list_search = false;   // wv_index_set_pq_list_search: flat queries of wv_search_batch_ids walk their lists
     uint64_t pq_stride = 0;
     std::vector<uint64_t> has_code;
     DevBuf pq_cent, pq_codes;

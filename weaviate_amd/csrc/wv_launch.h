@@ -72,6 +72,7 @@ hipError_t wv_launch_h16_gtau(const unsigned int* gtau, int nq, float sx, const 
                               hipStream_t s);
 float wv_h16_pow2_scale(float maxabs);
 hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s);
+hipError_t wv_launch_flat_ids_pq(const wv::FlatIdsPqParams* p, hipStream_t s);
 hipError_t wv_launch_ids_to_bits(const uint32_t* ids, const uint64_t* off, const int32_t* sel, int nsel,
                                  uint64_t max_len, uint64_t n_rows, uint64_t words, uint64_t* bits, hipStream_t s);
 hipError_t wv_launch_pq_topk(const float* skey, const uint32_t* sval, const float* dist, const uint32_t* rows,

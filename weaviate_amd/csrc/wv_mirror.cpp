@@ -351,6 +351,12 @@ struct wv_mirror {
         const wv_config cf = config();
         int rc = wv_index_create(d, metric, &cf, cap, &nb.ix);
         if (rc) { nb.ix = nullptr; return rc; }
+        // filtered reads reach a compressed shard as id lists (the batcher):
+        // they walk the lists over the codes -- same answers as the bitmap route
+#ifndef WV_TSAN_BUILD   // (the ThreadSanitizer build's CPU index has no such entry point, and takes no id lists)
+        rc = wv_index_set_pq_list_search(nb.ix, 1);
+        if (rc) return rc;
+#endif
         rc = wv_batcher_create(nb.ix, d, opt.max_batch, opt.max_wait_us, &nb.b);
         if (rc) { nb.b = nullptr; return rc; }
         nb.dim = d;

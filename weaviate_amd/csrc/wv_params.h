@@ -450,6 +450,32 @@ struct FlatIdsParams {
 };
 constexpr int FLAT_IDS_DPAD_MAX = 8192;   // the query row lives in LDS
 
+// Flat search over per-query id lists on a compressed index (wv_flat_ids.hip,
+// flat_ids_pq_kernel): FlatIdsParams' lists, selection and outputs, the
+// distance from the codes (pq_dist_row's bits, from the workgroup's lookup
+// table where its chunk holds at least lut_min_rows ids).  `lut` as in
+// SbdPqParams; lut_min_rows and the launch's LDS are set by the launcher.
+struct FlatIdsPqParams {
+    const float* Q;           // [nq][dpad] (normalized if cosine)
+    const uint64_t* excl;     // tombstone | nil node | no vector | no code
+    uint64_t excl_nbits;
+    const uint32_t* ids;      // every query's list, ascending within a query
+    const uint64_t* off;      // [nq + 1] into ids
+    const int32_t* sel;       // [ns] batch rows the kernel answers
+    uint64_t n_rows;          // ids >= n_rows are skipped
+    uint64_t id_base;
+    uint64_t chunk_len;       // ids per workgroup (a multiple of 256)
+    unsigned long long* part; // [ns][n_chunks][k] sorted keys (n_chunks > 1)
+    int ns, n_chunks;
+    int dpad, metric, k;
+    uint64_t* out_ids;        // [nq][k], row sel[s]
+    float* out_d;
+    int32_t* out_n;
+    PqParams pq;
+    int lut;
+    uint64_t lut_min_rows;
+};
+
 // Flat search over PQ codes (flat_search.go:19-74 on a compressed index):
 // distances of a chunk of queries against a row list, keyed for a stable
 // segmented sort by (dist, row).

@@ -1375,6 +1375,34 @@ void ids_chunks(const wv_index* ix, int ns, uint64_t max_len, uint64_t* chunk_le
     *chunk_len = std::max<uint64_t>(256, ((max_len + nc - 1) / nc + 255) / 256 * 256);
     *n_chunks = std::max<uint64_t>(1, (max_len + *chunk_len - 1) / *chunk_len);
 }
+
+// Switches of the list kernel on a compressed index, read per call.
+// WV_FLAT_IDS_PQ_LUT=0|1: every workgroup evaluates rows directly / from the
+// lookup table wherever it fits; unset: the table where the workgroup's chunk
+// holds at least ks ids (as WV_SBD_PQ_LUT).
+static int flat_ids_pq_lut() {
+    const char* e = std::getenv("WV_FLAT_IDS_PQ_LUT");
+    return e && *e ? (std::atoi(e) ? 1 : 0) : -1;
+}
+// ids_chunks cuts a long list into chunks as short as 256 ids when few queries
+// are in flight, below the ks ids from which a workgroup builds the table.
+// Where the table may be used, a chunk is at least 4 ks ids (whole wave
+// rounds): a build costs what ks direct rows cost, so it is spread over four
+// times that.  Measured against no floor, ks, 16 ks and the scan pass's
+// 4 ks ds (profiles/flat_ids_pq/README.md): up to 1.8 x faster than no floor
+// on long lists of small batches; slower only for 1-8 queries with lists of a
+// few 4 ks on a 64 KiB table.  WV_FLAT_IDS_PQ_CHUNK=<ids> overrides the floor
+// (0: none; A/B runs).
+static void flat_ids_pq_chunk_floor(const wv::PqParams& pq, int lut, uint64_t max_len, uint64_t* chunk_len,
+                                    uint64_t* n_chunks) {
+    if (lut == 0 || (uint64_t)pq.m * pq.ks * 4 > (uint64_t)wv::SBD_PQ_LUT_BYTES_MAX) return;
+    uint64_t floor = 4 * (uint64_t)pq.ks;
+    if (const char* e = std::getenv("WV_FLAT_IDS_PQ_CHUNK")) floor = (uint64_t)std::max(0ll, std::atoll(e));
+    floor = (floor + 255) / 256 * 256;
+    if (*chunk_len >= floor) return;
+    *chunk_len = floor;
+    *n_chunks = std::max<uint64_t>(1, (max_len + floor - 1) / floor);
+}
 }  // namespace wv_host
 
 extern "C" {
@@ -1436,8 +1464,9 @@ int wv_search_batch(wv_index* ix, const float* queries, int nq, int k, int ef, c
 
 // wv_search_batch with one allow list per query, as ids.  The flat-versus-HNSW
 // rule of search.go:64-79 is applied on the host from each list's length; a
-// flat query whose list is short goes to the sparse kernel (wv_flat_ids.hip),
-// every other query to search_core over bitmap rows scattered on the device.
+// flat query whose list is short goes to the sparse kernel (wv_flat_ids.hip;
+// on a compressed index its PQ variant, where wv_index_set_pq_list_search is
+// on), every other query to search_core over bitmap rows scattered on the device.
 int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int ef, const uint64_t* allow_ids,
                         const uint64_t* allow_offsets, int mode, uint64_t* out_ids, float* out_dists, int32_t* out_n) {
     if (nq < 0) return fail(WV_EINVAL, "wv_search_batch_ids: nq < 0");
@@ -1481,7 +1510,10 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
         const uint64_t N = ix->n_rows;
         const int ef_eff = ef <= 0 ? search_time_ef(ix->cfg, k) : ef;
         const bool can_hnsw = ix->has_graph && ef_eff <= wv::HNSW_EF_MAX;
-        const bool sparse_ok = !ix->pq_on && k <= wv::BF_WIDE_KMAX && ix->dpad <= wv::FLAT_IDS_DPAD_MAX;
+        // (compressed: the list kernel over the codes, where the index asks
+        // for it -- its query row stays in memory, so any dimension)
+        const bool sparse_ok = k <= wv::BF_WIDE_KMAX &&
+                               (ix->pq_on ? ix->pq_list_search : ix->dpad <= wv::FLAT_IDS_DPAD_MAX);
         std::vector<int32_t> sel[3];   // sparse, bitmap rows searched flat, bitmap rows searched by HNSW
         uint64_t sp_ids = 0, sp_max = 0;
         for (int q = 0; q < nq; ++q) {
@@ -1510,37 +1542,54 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
             const int ns = (int)sel[0].size();
             uint64_t chunk_len = 0, nc = 0;
             ids_chunks(ix, ns, sp_max, &chunk_len, &nc);
-            wv::FlatIdsParams fp{};
-            fp.X = ix->vecs.as<float>();
-            fp.Q = dq;
-            fp.excl = ix->excl.as<uint64_t>();
-            fp.excl_nbits = ix->capacity;
-            fp.ids = ix->fi_ids.as<uint32_t>();
-            fp.off = ix->fi_off.as<uint64_t>();
-            fp.sel = ix->fi_sel.as<int32_t>();
-            fp.n_rows = N;
-            fp.id_base = ix->cfg.id_base;
-            fp.chunk_len = chunk_len;
-            fp.ns = ns;
-            fp.n_chunks = (int)nc;
-            if (nc > 1) {
-                HIP_TRY(ix->fi_part.ensure((size_t)ns * nc * k * 8));
-                fp.part = ix->fi_part.as<unsigned long long>();
+            wv::PqParams pq{};
+            int lut = -1;
+            if (ix->pq_on) {
+                pq = pq_params(ix);
+                lut = flat_ids_pq_lut();
+                flat_ids_pq_chunk_floor(pq, lut, sp_max, &chunk_len, &nc);
             }
-            fp.D = ix->dim;
-            fp.dpad = ix->dpad;
-            fp.ldx = ix->ldx;
-            fp.metric = ix->metric;
-            fp.k = k;
-            fp.out_ids = ix->out_ids.as<uint64_t>();
-            fp.out_d = ix->out_d.as<float>();
-            fp.out_n = ix->out_n.as<int32_t>();
+            if (nc > 1) HIP_TRY(ix->fi_part.ensure((size_t)ns * nc * k * 8));
+            // what both list kernels read: the lists, the selection, the outputs
+            auto fill = [&](auto& fp) {
+                fp.Q = dq;
+                fp.excl = ix->excl.as<uint64_t>();
+                fp.excl_nbits = ix->capacity;
+                fp.ids = ix->fi_ids.as<uint32_t>();
+                fp.off = ix->fi_off.as<uint64_t>();
+                fp.sel = ix->fi_sel.as<int32_t>();
+                fp.n_rows = N;
+                fp.id_base = ix->cfg.id_base;
+                fp.chunk_len = chunk_len;
+                fp.ns = ns;
+                fp.n_chunks = (int)nc;
+                if (nc > 1) fp.part = ix->fi_part.as<unsigned long long>();
+                fp.dpad = ix->dpad;
+                fp.metric = ix->metric;
+                fp.k = k;
+                fp.out_ids = ix->out_ids.as<uint64_t>();
+                fp.out_d = ix->out_d.as<float>();
+                fp.out_n = ix->out_n.as<int32_t>();
+            };
             if (ix->timing) {
                 for (auto& e : ix->fi_ev)
                     if (!e) HIP_TRY(hipEventCreate(&e));
                 HIP_TRY(hipEventRecord(ix->fi_ev[0], s));
             }
-            HIP_TRY(wv_launch_flat_ids(&fp, s));
+            if (ix->pq_on) {
+                wv::FlatIdsPqParams fp{};
+                fill(fp);
+                fp.pq = pq;
+                fp.lut = lut;
+                HIP_TRY(wv_launch_flat_ids_pq(&fp, s));
+            } else {
+                wv::FlatIdsParams fp{};
+                fill(fp);
+                fp.X = ix->vecs.as<float>();
+                fp.D = ix->dim;
+                fp.ldx = ix->ldx;
+                HIP_TRY(wv_launch_flat_ids(&fp, s));
+            }
             if (ix->timing) {
                 HIP_TRY(hipEventRecord(ix->fi_ev[1], s));
                 ix->fi_timed = true;

@@ -268,6 +268,12 @@ class GPUVectorIndex:
         """h.compressed: every search ranks by the PQ distance."""
         check(lib().wv_index_set_compressed(self._h, int(on)))
 
+    def set_pq_list_search(self, on: bool = True):
+        """Flat queries of search_batch_ids on a compressed index walk their
+        lists over the codes (on) or take the bitmap route (off, the default).
+        Same answers; no effect on an uncompressed index."""
+        check(lib().wv_index_set_pq_list_search(self._h, int(on)))
+
     def set_tombstones(self, ids: Iterable[int]):
         al = AllowList.from_ids(ids, self.capacity)
         check(lib().wv_index_set_tombstones(self._h, _ptr(al.words), al.nbits))

@@ -180,6 +180,57 @@ enum { WV_PQ_TILE = 0, WV_PQ_KMEANS = 1 };
 int wv_pq_code_len(int segments, int centroids, int use_bits_encoding);
 int wv_index_set_pq(wv_index *ix, int segments, int centroids, int use_bits_encoding, int encoder,
                     const float *centroid_table);
+/* ProductQuantizer.Fit with KMeans encoders (product_quantization.go:312-336,
+ * kmeans.go:118-226) on the device, over the resident rows.
+ * Data: the rows of [0, n_rows) that hold a vector, in ascending id
+ * (cleanData, compress.go:62-69); n their number, j = 0..n-1 a row's position
+ * in that order.  Tombstones play no part (cache.all() does not look at them);
+ * cosine rows are the normalized resident rows; segments <= 0 means dim
+ * (compress.go:54-56).
+ * Per segment s, independently: x_j = row j's slice [s ds, (s+1) ds),
+ * points[j] = 0, and for i = 0, 1, ...:
+ *   1. recluster: c = Nearest(x_j), wv_index_pq_encode's rule exactly (asm.L2
+ *      whatever the index metric, kmeans.go:48; centres ascending, the LAST
+ *      of equal distances wins); changes counts the j with points[j] != c,
+ *      then points[j] = c; a cluster's member list is its j in ascending order.
+ *   2. empty clusters (resortOnEmptySets), in ascending ci, take a donor j =
+ *      draw(a) = mix64(seed * 0xD1B54A32D192ED03 + ctr * 0x9E3779B97F4A7C15 + 1)
+ *      mod n, ctr = s << 40 | i << 32 | ci << 8 | a, mix64 the level draw's
+ *      mixer of wv_index_build_graph: a = 0..63 until the donor's current
+ *      cluster has more than one member; if all 64 fail, j + 1, j + 2, ...
+ *      (mod n) from the last draw to the first such point (one exists: n >=
+ *      centroids).  Then, as the reference does: ci's list becomes [j],
+ *      points[j] = ci, j STAYS in its old cluster's list (whose length does
+ *      not change), changes = n.  A cluster filled this way never donates.
+ *   3. if changes > 0, every centre is recomputed: per dimension the fp32 sum
+ *      of the members' values in list order from +0, one add per member, no
+ *      fusing, then one correctly rounded division by float32(list length).
+ *   4. stop if i >= 10 or changes < int(float32(n) * float32(0.01)) (an fp32
+ *      product, truncated); otherwise go on while changes > 0.
+ * Initial centres: init_table if given (NewKMeansWithCenters; duplicates are
+ * legal), else centre i of segment s is the slice of the row at position
+ * draw with ctr = s << 40 | 15 << 32 | i << 8 (with replacement, initCenters).
+ * The same index, arguments and seed give the same bits on every run.
+ * On success the index is as wv_index_set_pq(ix, segments, centroids,
+ * use_bits_encoding, WV_PQ_KMEANS, fitted table) would have left it: the
+ * table resident, the codes cleared, no row has a code, compressed off;
+ * wv_index_pq_encode then wv_index_set_compressed(ix, 1) complete Compress.
+ * out_iterations[s] = assignment passes run for segment s; *out_reseeded =
+ * empty clusters given a donor, all segments and rounds.
+ * Errors, before the index is touched: WV_EINVAL (a null index, segments not
+ * dividing dim, centroids outside 2..65536); WV_ESTATE (n < centroids, the
+ * reference's "Too few data to fit KMeans"; more than 2^31 - 1 rows; the index
+ * is compressed: switch it off first).  A device error after that leaves the
+ * index without a quantizer.  Blocks; runs on the index's stream under its
+ * mutex like wv_index_build_graph, and must not race with uploads.  Segments
+ * are fitted in groups whose sort buffers stay within 1 GiB (one segment's
+ * where n alone outgrows that).  Not fitted here: the tile encoder. */
+int wv_index_fit_pq(wv_index *ix, int segments, int centroids, int use_bits_encoding,
+                    const float *init_table /* nullable [segments][centroids][dim/segments] */,
+                    uint64_t seed,
+                    float *out_table        /* nullable, same shape */,
+                    int32_t *out_iterations /* nullable [segments]: assignment passes run */,
+                    uint64_t *out_reseeded  /* nullable: empty clusters given a donor, all segments */);
 int wv_index_upload_pq_codes(wv_index *ix, const uint8_t *encoded, uint64_t n, uint64_t first_id);
 int wv_index_pq_encode(wv_index *ix);
 /* the device codes of rows first_id.., one uint16 per segment: out[n][segments] */

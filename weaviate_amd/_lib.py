@@ -90,6 +90,7 @@ SIGNATURES = {
     "wv_index_delta_size": (C.c_int, [_vp, _u64p]),
     "wv_pq_code_len": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "wv_index_set_pq": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "wv_index_fit_pq": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, _vp, _vp, _u64p]),
     "wv_index_upload_pq_codes": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "wv_index_pq_encode": (C.c_int, [_vp]),
     "wv_index_download_pq_codes": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),

@@ -647,6 +647,144 @@ int wv_index_set_pq(wv_index* ix, int segments, int centroids, int use_bits_enco
     return WV_OK;
 }
 
+namespace {
+// scratch of one wv_index_fit_pq call, returned when it ends
+struct FitScratch {
+    DevBuf rowmap, active, points, changes, key, val, skey, sval, start, donor, reseeded, sort;
+    ~FitScratch() {
+        for (DevBuf* b : {&rowmap, &active, &points, &changes, &key, &val, &skey, &sval, &start, &donor, &reseeded, &sort})
+            b->release();
+    }
+};
+// bytes per (row, segment) of a group: points, the pairs in and out, and the
+// radix sort's own copy of both
+constexpr uint64_t FIT_PAIR_BYTES = 28;
+constexpr uint64_t FIT_GROUP_BYTES = 1ull << 30;
+}  // namespace
+
+int wv_index_fit_pq(wv_index* ix, int segments, int centroids, int use_bits_encoding, const float* init_table,
+                    uint64_t seed, float* out_table, int32_t* out_iterations, uint64_t* out_reseeded) {
+    if (!ix) return fail(WV_EINVAL, "wv_index_fit_pq: null index");
+    if (segments <= 0) segments = ix->dim;   // compress.go:54-56
+    CodeLayout L;
+    if (ix->dim % segments || !L.init(centroids, use_bits_encoding != 0))
+        return fail(WV_EINVAL, "wv_index_fit_pq: bad argument (segments must divide dims, 2 <= centroids <= 65536)");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->pq_on) return fail(WV_ESTATE, "wv_index_fit_pq: the index is compressed (wv_index_set_compressed(ix, 0) first)");
+    // cleanData (compress.go:62-69): the rows that hold a vector, in id order
+    uint64_t n = 0;
+    for (uint64_t w = 0; w < ix->bm_words; ++w) n += (uint64_t)__builtin_popcountll(ix->has_vec[w]);
+    if (n < (uint64_t)centroids) return fail(WV_ESTATE, "wv_index_fit_pq: too few data to fit KMeans (rows < centroids)");
+    if (n > 0x7FFFFFFFull) return fail(WV_ESTATE, "wv_index_fit_pq: more than 2^31 - 1 rows");
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    hipStream_t s = ix->stream;
+    const int ds = ix->dim / segments;
+    ix->pq_set = false;   // until the fit is complete
+    ix->pq_m = segments;
+    ix->pq_ks = centroids;
+    ix->pq_ds = ds;
+    ix->pq_encoder = WV_PQ_KMEANS;
+    ix->pq_use_bits = use_bits_encoding != 0;
+    ix->pq_stride = centroids > 256 ? ((2 * (uint64_t)segments + 7) & ~7ull) : (((uint64_t)segments + 3) & ~3ull);
+    const size_t tbytes = (size_t)segments * centroids * ds * 4;
+    HIP_TRY(ix->pq_cent.ensure(tbytes));
+    HIP_TRY(ix->pq_codes.ensure(ix->capacity * ix->pq_stride));
+
+    FitScratch sc;
+    wv::PqFitParams p{};
+    p.X = ix->vecs.as<float>();
+    p.ldx = ix->ldx;
+    p.n = n;
+    p.ks = centroids;
+    p.ds = ds;
+    p.cc = wv_pq_fit_chunk_centres(centroids, ds);
+    p.seed = seed;
+    p.cent = ix->pq_cent.as<float>();
+    if (n != ix->n_rows) {   // holes: position -> row
+        std::vector<uint32_t> rows;
+        rows.reserve(n);
+        for (uint64_t i = 0; i < ix->n_rows; ++i)
+            if (ix->has_vec[i >> 6] & (1ull << (i & 63))) rows.push_back((uint32_t)i);
+        HIP_TRY(sc.rowmap.ensure(n * 4));
+        HIP_TRY(hipMemcpyAsync(sc.rowmap.p, rows.data(), n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        p.rowmap = sc.rowmap.as<uint32_t>();
+    }
+    if (init_table) HIP_TRY(hipMemcpyAsync(p.cent, init_table, tbytes, hipMemcpyHostToDevice, s));
+    else HIP_TRY(wv_launch_pq_fit_init(&p, segments, s));
+
+    // segments per group: the sort buffers stay within FIT_GROUP_BYTES (one
+    // segment's where n alone outgrows that), the pair count within an int
+    const int group = (int)std::max<uint64_t>(
+        1, std::min<uint64_t>({(uint64_t)segments, FIT_GROUP_BYTES / (FIT_PAIR_BYTES * n), 0x7FFFFFFFull / n}));
+    HIP_TRY(sc.active.ensure((size_t)group * 4));
+    HIP_TRY(sc.changes.ensure((size_t)group * 4));
+    HIP_TRY(sc.reseeded.ensure(8));
+    for (DevBuf* b : {&sc.points, &sc.key, &sc.val, &sc.skey, &sc.sval}) HIP_TRY(b->ensure((size_t)group * n * 4));
+    HIP_TRY(sc.start.ensure(((size_t)group * centroids + 1) * 4));
+    HIP_TRY(sc.donor.ensure((size_t)group * centroids * 4));
+    p.active = sc.active.as<int32_t>();
+    p.points = sc.points.as<uint32_t>();
+    p.changes = sc.changes.as<uint32_t>();
+    p.key = sc.key.as<uint32_t>();
+    p.val = sc.val.as<uint32_t>();
+    p.skey = sc.skey.as<uint32_t>();
+    p.sval = sc.sval.as<uint32_t>();
+    p.start = sc.start.as<uint32_t>();
+    p.donor = sc.donor.as<uint32_t>();
+    p.reseeded = sc.reseeded.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(p.reseeded, 0, 8, s));
+
+    // stopCondition (kmeans.go:191-194): an fp32 product, truncated
+    const float delta = (float)n * 0.01f;
+    const int64_t min_changes = (int64_t)delta;
+    std::vector<int32_t> iters((size_t)segments, 0), act;
+    std::vector<uint32_t> chg;
+    for (int s0 = 0; s0 < segments; s0 += group) {
+        p.s0 = s0;
+        p.ng = std::min(group, segments - s0);
+        act.assign((size_t)p.ng, 1);
+        chg.assign((size_t)p.ng, 0);
+        size_t sort_bytes = 0;
+        HIP_TRY(wv_pq_fit_sort(&p, nullptr, &sort_bytes, s));
+        HIP_TRY(sc.sort.ensure(sort_bytes));
+        sort_bytes = sc.sort.cap;
+        HIP_TRY(hipMemsetAsync(p.points, 0, (size_t)p.ng * n * 4, s));   // m.data.points = make([]uint64, dataSize)
+        HIP_TRY(wv_launch_pq_fit_iota(&p, s));
+        for (int i = 0;; ++i) {
+            p.iter = i;
+            HIP_TRY(hipMemcpyAsync(sc.active.p, act.data(), (size_t)p.ng * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(p.changes, 0, (size_t)p.ng * 4, s));
+            HIP_TRY(wv_launch_pq_fit_assign(&p, s));
+            HIP_TRY(wv_pq_fit_sort(&p, sc.sort.p, &sort_bytes, s));
+            HIP_TRY(wv_launch_pq_fit_empty(&p, s));
+            HIP_TRY(wv_launch_pq_fit_centres(&p, s));
+            HIP_TRY(hipMemcpyAsync(chg.data(), p.changes, (size_t)p.ng * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            bool any = false;
+            for (int sl = 0; sl < p.ng; ++sl) {
+                if (!act[sl]) continue;
+                iters[s0 + sl] = i + 1;
+                if (i >= 10 || (int64_t)chg[sl] < min_changes || chg[sl] == 0) act[sl] = 0;
+                else any = true;
+            }
+            if (!any) break;
+        }
+    }
+    unsigned long long reseeded = 0;
+    HIP_TRY(hipMemcpyAsync(&reseeded, p.reseeded, 8, hipMemcpyDeviceToHost, s));
+    if (out_table) HIP_TRY(hipMemcpyAsync(out_table, p.cent, tbytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(ix->pq_codes.p, 0, ix->capacity * ix->pq_stride, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_iterations) std::copy(iters.begin(), iters.end(), out_iterations);
+    if (out_reseeded) *out_reseeded = reseeded;
+    ix->has_code.assign(ix->bm_words, 0);
+    ix->pq_set = true;
+    ix->pq_on = false;
+    ix->bitmaps_dirty = true;
+    return WV_OK;
+}
+
 int wv_index_upload_pq_codes(wv_index* ix, const uint8_t* encoded, uint64_t n, uint64_t first_id) {
     if (check(ix) || (n && !encoded)) return fail(WV_EINVAL, "wv_index_upload_pq_codes: bad argument");
     std::lock_guard<std::mutex> g(ix->mu);

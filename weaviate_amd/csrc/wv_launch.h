@@ -47,6 +47,13 @@ hipError_t wv_launch_sbd_pq_ids(const wv::SbdPqIdsParams* p, hipStream_t s);
 hipError_t wv_launch_pq_encode(const float* X, int ldx, const uint64_t* ids, uint64_t n_rows, const wv::PqParams* pq,
                                uint8_t* codes, hipStream_t s);
 hipError_t wv_launch_pq_scan(const wv::PqScanParams* p, hipStream_t s);
+hipError_t wv_launch_pq_fit_init(const wv::PqFitParams* p, int segments, hipStream_t s);
+hipError_t wv_launch_pq_fit_iota(const wv::PqFitParams* p, hipStream_t s);
+int wv_pq_fit_chunk_centres(int ks, int ds);
+hipError_t wv_launch_pq_fit_assign(const wv::PqFitParams* p, hipStream_t s);
+hipError_t wv_pq_fit_sort(const wv::PqFitParams* p, void* scratch, size_t* scratch_bytes, hipStream_t s);
+hipError_t wv_launch_pq_fit_empty(const wv::PqFitParams* p, hipStream_t s);
+hipError_t wv_launch_pq_fit_centres(const wv::PqFitParams* p, hipStream_t s);
 hipError_t wv_launch_split_rows(const float* in, int ld_in, const uint64_t* ids, uint64_t n, uint64_t n_valid, int D,
                                 float scale, void* out, int ld_out, uint64_t out_row0, hipStream_t s);
 hipError_t wv_launch_h16_rows(const float* in, int ld_in, const uint64_t* ids, uint64_t n, int D, int ns, float sign,

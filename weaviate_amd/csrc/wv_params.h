@@ -515,6 +515,32 @@ struct SbdPqIdsParams {
     uint64_t lut_min_rows;
 };
 
+// KMeans fitting of the product quantizer (wv_pq_fit.hip; kmeans.go:118-226):
+// one round of a group of ng segments [s0, s0 + ng) over the n rows that hold
+// a vector (position j = rowmap[j]'s rank, ascending id).  Per-group arrays
+// are indexed by the segment's place in the group.
+struct PqFitParams {
+    const float* X;           // resident rows [..][ldx]
+    const uint32_t* rowmap;   // [n] position -> row (nullable: rows 0..n-1)
+    uint64_t n;
+    int ldx, ks, ds;
+    int s0, ng;
+    int cc;                   // centres per LDS chunk of the assignment pass (0: read from the table)
+    int iter;                 // the round i (the donor draw's counter)
+    uint64_t seed;
+    float* cent;              // the whole table [segments][ks][ds]
+    const int32_t* active;    // [ng] 0 = the segment has stopped
+    uint32_t* points;         // [ng][n] m.data.points
+    uint32_t* changes;        // [ng] m.data.changes of this round
+    uint32_t* key;            // [ng][n] place * ks + cluster, by position
+    uint32_t* val;            // [ng][n] j
+    uint32_t* skey;           // the pairs sorted by key, equal keys in ascending j
+    uint32_t* sval;
+    uint32_t* start;          // [ng * ks + 1] first sorted position of every (segment, cluster)
+    uint32_t* donor;          // [ng][ks] the point an empty cluster was given (~0: none)
+    unsigned long long* reseeded;   // += empty clusters given a donor
+};
+
 // GPU graph construction: one batch of new nodes
 // [first, first + nb), inserted against the graph of the h.N nodes before it.
 struct BuildParams {

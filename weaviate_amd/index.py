@@ -247,6 +247,37 @@ class GPUVectorIndex:
         check(lib().wv_index_set_pq(self._h, cent.shape[0], cent.shape[1], int(use_bits_encoding),
                                     {"tile": 0, "kmeans": 1}[encoder], _ptr(cent)))
 
+    def fit_pq(self, segments: int, centroids: int, use_bits_encoding: bool = False, init=None, seed: int = 0):
+        """ProductQuantizer.Fit with KMeans encoders on the device, over the
+        rows that hold a vector (wv_index_fit_pq); segments <= 0 means dim.
+        `init`: the starting centres [segments][centroids][dims/segments]
+        (default: rows drawn from `seed`).  Leaves the index as set_pq(table)
+        does.  Returns (table, iterations[segments], reseeded)."""
+        m = segments if segments > 0 else self.dim
+        if self.dim % m or centroids < 1:
+            raise WvError(1, f"segments must divide dims ({self.dim}), got {segments}")
+        shape = (m, centroids, self.dim // m)
+        ini = None
+        if init is not None:
+            ini = np.ascontiguousarray(init, dtype=np.float32)
+            if ini.shape != shape:
+                raise WvError(1, f"init must be {shape}, got {ini.shape}")
+        table = np.zeros(shape, np.float32)
+        iters = np.zeros(m, np.int32)
+        res = C.c_uint64()
+        check(lib().wv_index_fit_pq(self._h, m, centroids, int(use_bits_encoding), None if ini is None else _ptr(ini),
+                                    seed, _ptr(table), _ptr(iters), C.byref(res)))
+        self._pq = (m, centroids, bool(use_bits_encoding))
+        return table, iters, res.value
+
+    def compress(self, segments: int, centroids: int, use_bits_encoding: bool = False, init=None, seed: int = 0):
+        """Compress (compress.go:39-88): fit on every resident vector, encode
+        every vector, switch compressed on.  Returns fit_pq's result."""
+        fitted = self.fit_pq(segments, centroids, use_bits_encoding, init, seed)
+        self.pq_encode()
+        self.set_compressed(True)
+        return fitted
+
     def upload_pq_codes(self, encoded, first_id: int = 0):
         """Encoded vectors in ProductQuantizer.Encode's byte layout, uint8[n][code_len]."""
         enc = np.ascontiguousarray(encoded, dtype=np.uint8)

@@ -312,7 +312,8 @@ int wv_last_sbd_stats(wv_index *ix, uint64_t *pass_queries, uint64_t *hnsw_round
 
 /* Batched search of nq queries (row-major [nq][dim]).  ef <= 0 selects
  * searchTimeEF(k).  allow_bits may be NULL, one bitmap shared by the batch
- * (allow_stride_words == 0) or one bitmap per query.  out_* are [nq][k]. */
+ * (allow_stride_words == 0) or one bitmap per query.  out_* are [nq][k]; of a
+ * row only the first out_n[q] slots are written. */
 int wv_search_batch(wv_index *ix, const float *queries, int nq, int k, int ef, const uint64_t *allow_bits,
                     uint64_t allow_nbits, uint64_t allow_stride_words, int mode, uint64_t *out_ids,
                     float *out_dists, int32_t *out_n);

@@ -27,22 +27,11 @@ import pyoracle as O
 import weaviate_amd as W
 from bench import counter_gauss, counter_glove, counter_sift, counter_uniform
 from helpers import merge_lists, recall, same, same_tie_aware, tie_aware_equal
+from helpers import unexplained as _unexplained, unexplained_filtered as _unexplained_filtered
 
 pytestmark = pytest.mark.gpu
 
 THREADS = 16
-
-
-def _unexplained(ref, qs, k, ef, gi, gd, oi, od):
-    """Queries whose GPU answer differs from the restatement's beyond tie
-    order, although the restatement took no decision between equal distances
-    (the reference orders equal distances by heap layout)."""
-    bad = []
-    for i in range(len(qs)):
-        if not tie_aware_equal(gi[i], gd[i], oi[i], od[i]):
-            if ref.knn_search(qs[i], k, ef, with_stats=True)[2]["ties"] == 0:
-                bad.append(i)
-    return bad
 
 
 def test_configs0_gpu_built_graph_recall_vs_sequential_build():
@@ -96,27 +85,6 @@ def test_configs0_sift_hnsw_m64_efc128_ef64():
     assert abs(r_gpu - r_cpu) <= 0.005, (r_gpu, r_cpu)
     assert r_gpu >= 0.95, r_gpu
     ix.close()
-
-
-def _unexplained_filtered(ref, qs, k, ef, words, gi, gd, gn, oi, od, on):
-    """Queries whose GPU answer is neither the restatement's (up to tie order)
-    nor explained: the restatement took a decision between equal distances
-    (heap layout), or the query fell back to the exact filtered
-    scan (its answer then equals flatSearch's: a superset in quality).
-    Returns (unexplained, answered-as-flatSearch)."""
-    bad, flat = [], []
-    for i in range(len(qs)):
-        if gn[i] == on[i] and tie_aware_equal(gi[i][:gn[i]], gd[i][:gn[i]], oi[i][:on[i]], od[i][:on[i]]):
-            continue
-        if ref.knn_search(qs[i], k, ef, allow=words, with_stats=True)[2]["ties"] > 0:
-            continue
-        fi, fd, fn, _ = ref.search_batch(qs[i:i + 1], k, ef, allow=words, mode=1)   # flatSearch
-        fi, fd, fn = fi[0], fd[0], int(fn[0])
-        if fn == gn[i] and tie_aware_equal(gi[i][:fn], gd[i][:fn], fi[:fn], fd[:fn]):
-            flat.append(i)
-            continue
-        bad.append(i)
-    return bad, flat
 
 
 def _variants_identical(ix, qs, k, ef, allow, ref_out, monkeypatch):

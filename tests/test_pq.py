@@ -12,8 +12,10 @@ kms[i].Centroid(c) (INTEGRATION.md).
 import numpy as np
 import pytest
 
+import helpers as H
 import pyoracle as O
 import weaviate_amd as W
+from helpers import tie_aware_equal, unexplained
 
 
 # ---------------------------------------------------------------- CPU: oracle KATs
@@ -94,6 +96,54 @@ def test_c_abi_code_length():
     assert W.lib().wv_pq_code_len(8, 1, 0) == -1
 
 
+@pytest.mark.parametrize("li", range(len(H.PQ_LAYOUTS)))
+def test_tie_share_of_the_compressed_search_cases_is_under_the_caps(li):
+    """tests/test_gpu_pq_search.py waives a query whose GPU answer differs where
+    the restatement took a decision between equal distances (ties > 0) and caps
+    the waived share per case.  The caps are conditions on the inputs, checked
+    here on the restatement alone: for exactly those rows, graphs, codes,
+    queries, lists and tombstones, the queries with ties > 0 -- the most a
+    comparison could waive -- stay under the cap of their case."""
+    filtered = set(H.pq_filtered_pairs())
+    for metric in H.PQ_METRICS:
+        c = H.pq_case_inputs(li, metric)
+        ref, qs = c["ref"], c["qs"]
+        for ef in H.PQ_EF_UNFILTERED:
+            for nq in (H.PQ_NQ, H.PQ_NQ + 3):
+                t = H.tie_share(ref, qs[:nq], H.PQ_K, ef)
+                assert t <= H.PQ_CAP_UNFILTERED * nq, (metric, ef, nq, t)
+        if (li, metric) not in filtered:
+            continue
+        qs = qs[:H.PQ_NQ]
+        shared = O.bits_from_ids(c["shared"], H.PQ_N)
+        per = [O.bits_from_ids(p, H.PQ_N) for p in c["per"]]
+        for ef in H.PQ_EF_FILTERED:
+            for words in (shared, per):
+                t = H.tie_share(ref, qs, H.PQ_K, ef, words)
+                assert t <= H.PQ_CAP_FILTERED * H.PQ_NQ, (metric, ef, t)
+        for dead in c["dead"]:
+            ref.add_tombstone(int(dead))
+        for ef in H.PQ_EF_FILTERED:
+            for words in (None, shared):
+                t = H.tie_share(ref, qs, H.PQ_K, ef, words)
+                assert t <= H.PQ_CAP_FILTERED * H.PQ_NQ, (metric, ef, t)
+        for dead in c["dead"]:
+            ref.remove_tombstone(int(dead))
+        if metric == "l2-squared" and li in H.PQ_CAP_SELECTIVE:
+            t = H.tie_share(ref, qs, H.PQ_K, 64, O.bits_from_ids(c["selective"], H.PQ_N))
+            print(f"layout {li}: selective list of {len(c['selective'])} rows, ties > 0 for {t} of {H.PQ_NQ} queries")
+            # the cap is the share measured here + 5 points, never above 25 %
+            assert t <= H.PQ_CAP_SELECTIVE[li] * H.PQ_NQ and t <= 0.25 * H.PQ_NQ, t
+            assert H.PQ_CAP_SELECTIVE[li] <= min(0.25, t / H.PQ_NQ + 0.05) + 1e-9
+        if metric != "cosine-dot" and li in (0, 2):     # rows added after the graph (ef 64)
+            a = H.pq_added_inputs(li, metric)
+            t = H.tie_share(a["ref"], qs, H.PQ_K, 64)
+            assert t <= H.PQ_CAP_UNFILTERED * H.PQ_NQ, (metric, t)
+            for words in (shared, per):
+                t = H.tie_share(a["ref"], qs, H.PQ_K, 64, words)
+                assert t <= H.PQ_CAP_FILTERED * H.PQ_NQ, (metric, t)
+
+
 # ---------------------------------------------------------------- GPU parity
 def _centroids(base, m, ks, seed=0):
     """A fitted-looking quantizer: per segment, ks distinct data rows' segments."""
@@ -113,12 +163,21 @@ def _same_tie_aware(a_ids, a_d, b_ids, b_d):
             assert set(a_ids[a_d == v].tolist()) == set(b_ids[b_d == v].tolist())
 
 
+def _encode_case(d, m, ks, use_bits):
+    # the d 32 cases keep their ids; the others carry d: ds 5 with rows padded
+    # from 30 to 32 floats (ldx != d), ds 1 with 4-bit packed input, 12-bit
+    # packed input (helpers.PQ_LAYOUTS 2, 5 and 6)
+    return pytest.param(d, m, ks, use_bits, id=f"{m}-{ks}-{use_bits}" if d == 32 else f"d{d}-{m}-{ks}-{use_bits}")
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("m,ks,use_bits", [(32, 256, False), (8, 256, False), (8, 64, True), (4, 1024, True),
-                                           (16, 1024, False)])
-def test_device_encode_equals_reference_encoder(m, ks, use_bits):
+@pytest.mark.parametrize("d,m,ks,use_bits", [_encode_case(32, 32, 256, False), _encode_case(32, 8, 256, False),
+                                             _encode_case(32, 8, 64, True), _encode_case(32, 4, 1024, True),
+                                             _encode_case(32, 16, 1024, False), _encode_case(30, 6, 256, False),
+                                             _encode_case(20, 20, 16, True), _encode_case(48, 6, 4096, True)])
+def test_device_encode_equals_reference_encoder(d, m, ks, use_bits):
     rng = np.random.default_rng(m + ks)
-    n, d = 3000, 32
+    n = 3000 if ks <= 2048 else 5000     # (the table is cut from ks distinct rows)
     base = rng.standard_normal((n, d)).astype(np.float32)
     cent = _centroids(base, m, ks)
     ix = W.GPUVectorIndex(d, "l2-squared", capacity=n)
@@ -133,6 +192,30 @@ def test_device_encode_equals_reference_encoder(m, ks, use_bits):
     ix.upload_pq_codes(enc)
     assert np.array_equal(ix.download_pq_codes(n), want)
     ix.close()
+
+
+@pytest.mark.gpu
+def test_device_encode_last_of_equal_centroids_wins():
+    """kmeans.go:78-110 on the device: centroids 1, 3 and 5 of the segment are
+    equal and the nearest, so the code is 5 (test_kmeans_nearest_last_tie_wins
+    pins the restatement)."""
+    cent = np.zeros((1, 8, 2), np.float32)
+    cent[0, :, 0] = [5, 1, 3, 1, 9, 1, 7, 2]
+    rows = np.random.default_rng(8).standard_normal((300, 2)).astype(np.float32)
+    rows[0] = [1.0, 0.0]
+    rows[1] = [1.25, 0.5]
+    ix = W.GPUVectorIndex(2, "l2-squared", capacity=len(rows))
+    ix.upload_vectors(rows)
+    ix.set_pq(cent)
+    ix.pq_encode()
+    got = ix.download_pq_codes(len(rows))
+    ix.close()
+    enc = O.pq_encode_kmeans(rows, cent)
+    want = np.array([O.pq_extract(enc[r].tobytes(), 1, 8) for r in range(len(rows))], np.uint16)
+    assert want[0, 0] == 5 and want[1, 0] == 5
+    assert got[0, 0] == 5
+    assert np.array_equal(got, want)
+    assert not np.isin(got, [1, 3]).any()      # never an earlier one of the equal centroids
 
 
 def _compressed_pair(n, d, m, ks, metric="l2-squared", M=16, efc=64, seed=5, use_bits=False):
@@ -198,9 +281,14 @@ def test_compressed_hnsw_parity(metric, ef):
     qs = rng.standard_normal((200, d)).astype(np.float32)
     gi, gd, gn = ix.search_batch(qs, k, ef=ef, mode="hnsw")
     oi, od, on, _ = ref.search_batch(qs, k, ef, threads=8)
-    same = sum(np.array_equal(gd[i, : gn[i]].view(np.uint32), od[i, : on[i]].view(np.uint32)) for i in range(len(qs)))
-    assert same >= len(qs) - 2, same   # tie-dependent expansion order aside
     ix.close()
+    assert gn.tolist() == on.tolist()
+    # ids and distances, tie-aware; a differing query only where the restatement
+    # took a decision between equal distances, and at most 2 of those
+    bad, waived = unexplained(ref, qs, k, ef, gi, gd, oi, od, with_waived=True)
+    print(f"{metric} ef {ef}: tie-waived {len(waived)} of {len(qs)}")
+    assert not bad, bad
+    assert len(waived) <= 2, waived
 
 
 @pytest.mark.gpu
@@ -227,14 +315,27 @@ def test_compress_after_deletes_does_not_crash():
     ix.set_pq(cent)
     ix.pq_encode()
     ix.set_compressed(True)
-    hits = 0
-    for q in qs[:20]:
+    bad, waived, flat, fallbacks = [], [], [], 0
+    for i, q in enumerate(qs[:20]):
         ids, ds = ix.search_by_vector(q, k)
+        fallbacks += ix.last_batch_stats()["fallbacks"]
         assert len(ids) == k and not set(ids.tolist()) & set(dead)
-        oi, od = ref.search_by_vector(q, k)
-        hits += np.array_equal(ds.view(np.uint32), od.view(np.uint32))
-    assert hits >= 18
+        oi, od, st = ref.search_by_vector(q, k, with_stats=True)
+        if len(oi) == k and tie_aware_equal(ids, ds, oi, od):
+            continue
+        if st["ties"] > 0:       # the restatement took a decision between equal distances
+            waived.append(i)
+            continue
+        fi, fd, fn, _ = ref.search_batch(q[None], k, 0, mode=1)     # a reported fallback answers as flatSearch
+        if fn[0] == k and tie_aware_equal(ids, ds, fi[0], fd[0]):
+            flat.append(i)
+            continue
+        bad.append(i)
     ix.close()
+    print(f"tie-waived {len(waived)} of 20, answered as flatSearch {len(flat)}, fallbacks {fallbacks}")
+    assert not bad, bad
+    assert len(flat) <= fallbacks
+    assert len(waived) + len(flat) <= 2, (waived, flat)     # (18 of 20 as the restatement answers)
 
 
 @pytest.mark.gpu

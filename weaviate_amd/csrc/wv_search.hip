@@ -1403,6 +1403,27 @@ static void flat_ids_pq_chunk_floor(const wv::PqParams& pq, int lut, uint64_t ma
     *chunk_len = floor;
     *n_chunks = std::max<uint64_t>(1, (max_len + floor - 1) / floor);
 }
+// A batch's results from the pinned staging copy to the caller's arrays: the
+// counts, and of every row the first out_n[q] slots only.  The slots past a
+// count stay as the caller left them: the device buffers behind the staging
+// copy still hold earlier batches' results there (ids another batch's allow
+// list admitted).
+static void copy_results(const char* ids, const char* dists, const char* counts, int nq, int k, uint64_t* out_ids,
+                         float* out_dists, int32_t* out_n) {
+    std::memcpy(out_n, counts, (size_t)nq * 4);
+    bool full = true;
+    for (int q = 0; q < nq && full; ++q) full = out_n[q] == k;
+    if (full) {
+        std::memcpy(out_ids, ids, (size_t)nq * k * 8);
+        std::memcpy(out_dists, dists, (size_t)nq * k * 4);
+        return;
+    }
+    for (int q = 0; q < nq; ++q) {
+        const size_t n = (size_t)std::min(std::max(out_n[q], 0), k), o = (size_t)q * k;
+        std::memcpy(out_ids + o, ids + o * 8, n * 8);
+        std::memcpy(out_dists + o, dists + o * 4, n * 4);
+    }
+}
 }  // namespace wv_host
 
 extern "C" {
@@ -1456,9 +1477,7 @@ int wv_search_batch(wv_index* ix, const float* queries, int nq, int k, int ef, c
     }
     // the index is free for the next batch while this one finishes
     HIP_TRY(hipEventSynchronize(sl.done));
-    std::memcpy(out_ids, pin + o_i, ib);
-    std::memcpy(out_dists, pin + o_d, db);
-    std::memcpy(out_n, pin + o_n, nb);
+    copy_results(pin + o_i, pin + o_d, pin + o_n, nq, k, out_ids, out_dists, out_n);
     return WV_OK;
 }
 
@@ -1633,9 +1652,7 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
         HIP_TRY(hipEventRecord(sl.done, s));
     }
     HIP_TRY(hipEventSynchronize(sl.done));
-    std::memcpy(out_ids, pin + o_i, ib);
-    std::memcpy(out_dists, pin + o_d, db);
-    std::memcpy(out_n, pin + o_n, nb);
+    copy_results(pin + o_i, pin + o_d, pin + o_n, nq, k, out_ids, out_dists, out_n);
     return WV_OK;
 }
 

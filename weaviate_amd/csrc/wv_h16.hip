@@ -400,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
         // mask a half's ineligible rows to +inf (rows (r & 3) + 8 (r >> 2) of its 32)
         auto mask_half = [&](floatx16& A, floatx16& B, uint32_t oa, uint32_t ob) {
             constexpr uint32_t LANE_ROWS = 0x0F0F0F0Fu;
-            if (__all((oa & ob & LANE_ROWS) == LANE_ROWS)) return;
+            if (wave_all((oa & ob & LANE_ROWS) == LANE_ROWS)) return;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int bit = (r & 3) + 8 * (r >> 2);
@@ -555,13 +555,21 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16_kernel(H16Params p) {
             return false;
 #endif
             const bool x0 = m0 <= fminf(l0d[BF_KP - 1], pt0), x1 = m1 <= fminf(l1d[BF_KP - 1], pt1);
-            const bool any = __any(x0 || x1);
+            // (the votes as the two compares' own lane masks, taken where the
+            // compares are: their `or` sets SCC for the branch.  A vote on
+            // x0 || x1, or on x0 in another block, went mask -> v_cndmask 0 / 1
+            // -> v_cmp_ne -> VCC before the scalar branch, in every half)
+            const uint64_t b0 = __builtin_amdgcn_ballot_w64(x0), b1 = __builtin_amdgcn_ballot_w64(x1);
+            const bool any = (b0 | b1) != 0;
             if (__builtin_expect(any, 0)) {
                 WV_DBG_COUNT(3)
                 // (the smallest key by its position; the per-key scan only
                 // for a second key under the threshold: 2.645 -> 2.622 ms)
-                if (__any(x0)) min_extract(m0, x0, A, pt0, l0d, l0i, rb);
-                if (__any(x1)) min_extract(m1, x1, B, pt1, l1d, l1i, rb);
+                // (min_extract's position chain is inline asm the compiler's
+                // hazard checks do not see: every key of A / B was read by the
+                // VALU minima that made m0 / m1 before, as it requires)
+                if (b0 != 0) min_extract(m0, x0, A, pt0, l0d, l0i, rb);
+                if (b1 != 0) min_extract(m1, x1, B, pt1, l1d, l1i, rb);
             }
             return any;
         };
@@ -1081,11 +1089,13 @@ __global__ __launch_bounds__(512, 1) void wv_bf_h16w_kernel(H16Params p) {
                     const float th = fminf(ld[BF_KP - 1], pt);
                     const float m = min16(A);
                     const bool x = m <= th;
-                    if (__any(x)) {
+                    if (wave_any(x)) {
                         WV_DBG_COUNT(3)
                         // (the minimum by position, the per-key scan only for a
                         // second hit: 2.364 -> 2.249 ms per C4-shaped pass; A is
                         // reloaded from the C-in at the next tile)
+                        // (its position chain is inline asm: min16(A) above has
+                        // read every key of A with the VALU, as it requires)
                         min_extract(m, x, A, pt, ld, li, rr);
                     }
                 };

@@ -147,12 +147,21 @@ __device__ __forceinline__ void list_insert(float d, uint32_t id, float (&ld)[BF
         id = lt ? ti : id;
     }
 }
+// Wave votes as scalar compares of the ballot (s_cmp_*_u64 + s_cbranch_scc*).
+// The ballot folds into the VALU compare that made c only when that compare
+// stands in the same block and is c itself: a vote on `a || b`, or on a flag
+// computed in an earlier block, goes mask -> v_cndmask 0 / 1 -> v_cmp_ne ->
+// VCC before the branch (wv_h16.hip extract_half keeps the ballots instead).
+__device__ __forceinline__ bool wave_any(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0; }
+__device__ __forceinline__ bool wave_all(bool c) {
+    return __builtin_amdgcn_ballot_w64(c) == __builtin_amdgcn_ballot_w64(true);
+}
 __device__ __forceinline__ void ballot_extract(const floatx16& A, float thr, float (&ld)[BF_KP], uint32_t (&li)[BF_KP],
                                                uint32_t rb) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const bool c = A[r] <= thr;
-        if (__any(c)) {
+        if (wave_any(c)) {
             WV_DBG_COUNT(1)
             uint32_t id = rb;   // opaque: the row ids stay in this rare path
             asm volatile("" : "+v"(id));
@@ -161,29 +170,83 @@ __device__ __forceinline__ void ballot_extract(const floatx16& A, float thr, flo
     }
 }
 
+// The second smallest of a lane's 16 keys, counted with multiplicity (a
+// duplicate of the minimum is the second smallest), without knowing where the
+// minimum sits: the two smallest of five key triples (v_min3 / v_med3), then
+// the smaller of the smallest triple median and the second smallest of the
+// triple minima and key 15 -- the overall second is the median of the
+// minimum's triple or the minimum of another one.  19 VALU, no compare mask.
+__device__ __forceinline__ float second_min16(const floatx16& A) {
+    float lo[5], md[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        lo[i] = fminf(fminf(A[3 * i], A[3 * i + 1]), A[3 * i + 2]);
+        md[i] = __builtin_amdgcn_fmed3f(A[3 * i], A[3 * i + 1], A[3 * i + 2]);
+    }
+    const float la = fminf(fminf(lo[0], lo[1]), lo[2]), ma = __builtin_amdgcn_fmed3f(lo[0], lo[1], lo[2]);
+    const float lb = fminf(fminf(lo[3], lo[4]), A[15]), mb = __builtin_amdgcn_fmed3f(lo[3], lo[4], A[15]);
+    const float s = fminf(fminf(ma, mb), fmaxf(la, lb));
+    return fminf(fminf(fminf(md[0], md[1]), md[2]), fminf(fminf(md[3], md[4]), s));
+}
+
+// The lowest position r with A[r] == m (15 when none of keys 0-14 is: m is the
+// column's minimum), as the descending select chain
+//     pos = 15;  for r = 14 .. 0:  pos = A[r] == m ? r : pos
+// A VALU compare's lane mask may be read by a VALU select two instructions
+// later at the earliest on gfx950; the compiler put all fifteen compares
+// through one mask register and an s_nop 1 behind each (split chains and
+// opaque joins included: it allocates one SGPR pair again).  Written out, the
+// compares alternate between VCC and one SGPR pair and run two keys ahead of
+// the selects, so a compare, the older select and the next compare stand
+// between every mask's write and its read; the first and the last pair have
+// one instruction less there and an s_nop 0 instead.  The keys were all read
+// by the column minimum's VALU chain before: no MFMA result is read here first.
+#define WV_POS_STEP(r, mask, key)                                                              \
+    "v_cndmask_b32_e64 %0, %0, " #r ", " mask "\n\tv_cmp_eq_f32_e64 " mask ", " key ", %17\n\t"
+__device__ __forceinline__ int min_pos16(const floatx16& A, float m) {
+    int pos;
+    uint64_t t;
+    asm("v_cmp_eq_f32_e64 vcc, %16, %17\n\t"
+        "v_cmp_eq_f32_e64 %1, %15, %17\n\t"
+        "s_nop 0\n\t"
+        "v_cndmask_b32_e64 %0, 15, 14, vcc\n\t"
+        "v_cmp_eq_f32_e64 vcc, %14, %17\n\t"
+        WV_POS_STEP(13, "%1", "%13") WV_POS_STEP(12, "vcc", "%12") WV_POS_STEP(11, "%1", "%11")
+        WV_POS_STEP(10, "vcc", "%10") WV_POS_STEP(9, "%1", "%9") WV_POS_STEP(8, "vcc", "%8")
+        WV_POS_STEP(7, "%1", "%7") WV_POS_STEP(6, "vcc", "%6") WV_POS_STEP(5, "%1", "%5")
+        WV_POS_STEP(4, "vcc", "%4") WV_POS_STEP(3, "%1", "%3") WV_POS_STEP(2, "vcc", "%2")
+        "v_cndmask_b32_e64 %0, %0, 1, %1\n\t"
+        "s_nop 0\n\t"
+        "v_cndmask_b32_e64 %0, %0, 0, vcc"
+        : "=&v"(pos), "=&s"(t)
+        : "v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]), "v"(A[4]), "v"(A[5]), "v"(A[6]), "v"(A[7]), "v"(A[8]),
+          "v"(A[9]), "v"(A[10]), "v"(A[11]), "v"(A[12]), "v"(A[13]), "v"(A[14]), "v"(m)
+        : "vcc");
+    return pos;
+}
+#undef WV_POS_STEP
+
 // A column whose smallest key m is under its threshold (x, per lane): m goes
 // in straight from its position (a select chain, no per-key branch); the
 // column's other keys are scanned only when one of them is also under the
 // lane's threshold after the insertion (rare).  The list ends as after
 // ballot_extract(A, thr): a key between the new and the old tail falls off
-// the list either way.  A's entry at m's position is cleared to +inf.
+// the list either way.  Whether another key is under the threshold is asked of
+// the column's second smallest key (second_min16); A's entry at m's position
+// is cleared to +inf only where the scan then runs -- no caller reads the
+// accumulator after its extraction: the next MFMAs start from the C-in.
 __device__ __forceinline__ void min_extract(float m, bool x, floatx16& A, float pt, float (&ld)[BF_KP],
                                             uint32_t (&li)[BF_KP], uint32_t rb) {
-    int pos = 15;
-#pragma unroll
-    for (int r = 14; r >= 0; --r) pos = A[r] == m ? r : pos;
+    const int pos = min_pos16(A, m);
     uint32_t id = rb;   // opaque: the row ids stay in this rare path
     asm volatile("" : "+v"(id));
     if (x) list_insert(m, id + (uint32_t)((pos & 3) + 8 * (pos >> 2)), ld, li);
     const float thr2 = x ? fminf(ld[BF_KP - 1], pt) : -__builtin_inff();
-    float m2 = __builtin_inff();
+    if (__builtin_expect(wave_any(second_min16(A) <= thr2), 0)) {
 #pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-        A[r] = r == pos ? __builtin_inff() : A[r];
-        A[r + 1] = r + 1 == pos ? __builtin_inff() : A[r + 1];
-        m2 = fminf(fminf(m2, A[r]), A[r + 1]);
+        for (int r = 0; r < 16; ++r) A[r] = r == pos ? __builtin_inff() : A[r];
+        ballot_extract(A, thr2, ld, li, rb);
     }
-    if (__builtin_expect(__any(m2 <= thr2), 0)) ballot_extract(A, thr2, ld, li, rb);
 }
 
 // Certificate eps of the f16 key pass (true units): |key + offset - reference

@@ -7,8 +7,8 @@ flat / graph dispatch.
 Compressed HNSW: wv_hnsw_kernel<METRIC, PQ=true, NR> (wv_hnsw.hip) with
 pq_dist_row (wv_device.h); under a list or tombstones the LDS side-set kernel,
 its 2048-entry second pass and the per-query flat fallback (run_hnsw,
-wv_search.hip).  Flat: run_pq_flat (scan, segmented radix sort,
-wv_pq_topk_kernel).  Reference: search.go:171-199, index.go:493-511,
+wv_search_hnsw.hip).  Flat: run_pq_flat (wv_search_exact.hip: scan, segmented
+radix sort, wv_pq_topk_kernel).  Reference: search.go:171-199, index.go:493-511,
 flat_search.go:19-74 as restated in oracle/.
 
 A GPU answer that differs from the restatement's beyond tie order is accepted

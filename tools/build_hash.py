@@ -6,10 +6,11 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("wv_h16.hip", "wv_h16_dev.h", "wv_topk.h", "wv_search.hip", "wv_index.h", "wv_launch.h", "wv_params.h",
-           "wv_device.h")
+SOURCES = ("wv_h16.hip", "wv_h16_dev.h", "wv_topk.h", "wv_search_exact.hip", "wv_search.hip", "wv_search.h",
+           "wv_index.h", "wv_launch.h", "wv_params.h", "wv_device.h")
 # the HNSW search kernel and its launch
-SOURCES_HNSW = ("wv_hnsw.hip", "wv_search.hip", "wv_index.h", "wv_launch.h", "wv_params.h", "wv_device.h")
+SOURCES_HNSW = ("wv_hnsw.hip", "wv_search_hnsw.hip", "wv_search.hip", "wv_search.h", "wv_index.h", "wv_launch.h",
+                "wv_params.h", "wv_device.h")
 
 
 def build_hash(kernel: str = "wv_bf_h16_kernel") -> str:

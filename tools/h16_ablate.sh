@@ -11,9 +11,9 @@ if [ "$1" == "build" ]; then
   make -s -C $C ARCH=gfx950
   /opt/rocm/bin/hipcc $HF -x hip -c tools/h16_ablate.cpp -o $B/main.o
   # (queue_fbd's file with the ablation-only fallback skip: WV_ABLATE_NO_FALLBACK)
-  /opt/rocm/bin/hipcc $HF -DWV_ABLATION_BUILD -c $C/wv_search.hip -o $B/search.o
+  /opt/rocm/bin/hipcc $HF -DWV_ABLATION_BUILD -c $C/wv_search_exact.hip -o $B/search_exact.o
   # the library's objects, but for those two and the variant's wv_h16.o
-  OBJS=$(for o in $(make -s -C $C objs); do case $o in wv_h16.o) ;; wv_search.o) echo $B/search.o ;; *) echo $C/$o ;; esac; done)
+  OBJS=$(for o in $(make -s -C $C objs); do case $o in wv_h16.o) ;; wv_search_exact.o) echo $B/search_exact.o ;; *) echo $C/$o ;; esac; done)
   rm -f $B/abl_*
   for v in $VARIANTS; do
     name=${v%%=*}; defs=${v#*=}; defs=${defs//:/ }

@@ -2,7 +2,8 @@
 // and its device memory (vectors, norms, CSR graph, bitmaps).  Error state,
 // configuration, create/destroy, row upload and add, tombstones and the delta
 // set, capacity growth, product-quantizer setup, timing and stats.  Searches:
-// wv_search.hip, wv_distance.hip; graph construction: wv_build.hip.
+// wv_search.hip (with wv_search_exact.hip, wv_search_hnsw.hip),
+// wv_distance.hip; graph construction: wv_build.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>

@@ -10,8 +10,7 @@
 #include <cstdlib>
 
 #include "wv_device.h"
-#include "wv_index.h"
-#include "wv_launch.h"
+#include "wv_search.h"
 
 using namespace wv_host;
 

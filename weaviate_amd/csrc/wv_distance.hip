@@ -5,8 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "wv_index.h"
-#include "wv_launch.h"
+#include "wv_search.h"
 
 using namespace wv_host;
 
@@ -30,15 +29,9 @@ bool sbd_pq_enabled() {
     const char* e = std::getenv("WV_SBD_PQ");
     return !(e && e[0] == '0' && !e[1]);
 }
-int sbd_pq_lut() {
-    const char* e = std::getenv("WV_SBD_PQ_LUT");
-    return e && *e ? (std::atoi(e) ? 1 : 0) : -1;
-}
+int sbd_pq_lut() { return env_tri("WV_SBD_PQ_LUT"); }
 // entries of a query's list (WV_SBD_CAP, read per call)
-int sbd_cap() {
-    const char* e = std::getenv("WV_SBD_CAP");
-    return e ? std::max(128, std::atoi(e)) : 16384;
-}
+int sbd_cap() { return env_int("WV_SBD_CAP", 16384, 128); }
 
 // Round 1 (limit 100) of the queries that search by HNSW, on the host: slot[q]
 // is query q's row of ids / d ([nh][100]) and n ([nh]), -1 where round 1 is
@@ -173,9 +166,7 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
     HIP_TRY(hipSetDevice(ix->cfg.device));
     const uint64_t words = (allow_nbits + 63) / 64;
     const uint64_t astride = allow_stride_words ? allow_stride_words : words;
-    auto allow_of = [&](int q) -> const uint64_t* {
-        return allow_bits ? allow_bits + (allow_stride_words ? (uint64_t)q * allow_stride_words : 0) : nullptr;
-    };
+    auto allow_of = [&](int q) { return allow_row(allow_bits, allow_stride_words, q); };
     std::vector<int> legacy;   // queries for the per-query path
     std::vector<int> hnsw_q;   // queries whose round 1 is an HNSW search
     SbdRound1 r1(nq);
@@ -189,15 +180,16 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
             const int ef = search_time_ef(ix->cfg, 100);
             const bool can_hnsw = ix->has_graph && ef <= wv::HNSW_EF_MAX;
             for (int q = 0; q < nq; ++q) {
-                bool flat = !can_hnsw;
-                if (!flat && allow_bits && !ix->cfg.forbid_flat) {
-                    // allowList.Len() < flatSearchCutoff (search.go:74-78)
+                // allowList.Len() < flatSearchCutoff (search.go:74-78); no
+                // list: a length never below the cutoff (and none counted
+                // where the rule does not read it)
+                uint64_t c = INT64_MAX;
+                if (can_hnsw && allow_bits && !ix->cfg.forbid_flat) {
                     const uint64_t* a = allow_of(q);
-                    uint64_t c = 0;
+                    c = 0;
                     for (uint64_t w = 0; w < words; ++w) c += (uint64_t)__builtin_popcountll(a[w]);
-                    flat = (int64_t)c < ix->cfg.flat_search_cutoff;
                 }
-                if (!flat) {
+                if (!flat_by_len(ix, can_hnsw, c)) {
                     r1.slot[q] = (int)hnsw_q.size();
                     hnsw_q.push_back(q);
                 }
@@ -301,8 +293,9 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 HIP_TRY(ix->out_ids.ensure((size_t)nh * 100 * 8));
                 HIP_TRY(ix->out_d.ensure((size_t)nh * 100 * 4));
                 HIP_TRY(ix->out_n.ensure((size_t)nh * 4));
-                rc = search_core(ix, dq, nh, 100, 0, dal, allow_nbits, allow_stride_words, WV_MODE_AUTO,
-                                 ix->out_ids.as<uint64_t>(), ix->out_d.as<float>(), ix->out_n.as<int32_t>(), s);
+                const Batch b{dq, ix->dpad, nh, 100, dal, allow_nbits, allow_stride_words, ix->out_ids.as<uint64_t>(),
+                              ix->out_d.as<float>(), ix->out_n.as<int32_t>(), s};
+                rc = search_core(ix, b, 0, WV_MODE_AUTO);
                 if (rc) return rc;
                 HIP_TRY(hipMemcpyAsync(r1.ids.data(), ix->out_ids.p, (size_t)nh * 100 * 8, hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipMemcpyAsync(r1.d.data(), ix->out_d.p, (size_t)nh * 100 * 4, hipMemcpyDeviceToHost, s));
@@ -382,7 +375,7 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
     if (nq == 0) return WV_OK;
     const uint64_t total = allow_offsets[nq];
     const int cap = sbd_cap();
-    uint64_t max_entries = 1ull << 26;
+    uint64_t max_entries = 1ull << 26;   // (64-bit: its own parse)
     if (const char* e = std::getenv("WV_SBD_IDS_MAX_ENTRIES")) max_entries = std::strtoull(e, nullptr, 10);
     max_entries = std::min<uint64_t>(std::max<uint64_t>(max_entries, 1), 0x7FFFFFFFull);
     std::vector<int> legacy;   // queries for the per-query path
@@ -392,13 +385,14 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
     uint64_t N = 0;
     HIP_TRY(hipSetDevice(ix->cfg.device));
     {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t qb = (size_t)nq * ix->dim * 4, lb = (size_t)total * 4, fb = ((size_t)nq + 1) * 8,
                      tb = (size_t)nq * 4;
-        const size_t o_l = al(qb), o_f = o_l + al(lb), o_t = o_f + al(fb), need = o_t + al(tb);
+        PinLayout lay;
+        lay.add(qb);   // (the queries, at 0)
+        const size_t o_l = lay.add(lb), o_f = lay.add(fb), o_t = lay.add(tb);
         SlotLease lease(ix);
         wv_index::HostSlot& sl = *lease.sl;
-        if (int rc = slot_reserve(sl, need)) return rc;
+        if (int rc = slot_reserve(sl, lay.need())) return rc;
         char* pin = static_cast<char*>(sl.pin);
         std::memcpy(pin, queries, qb);
         std::memcpy(pin + o_t, targets, tb);
@@ -433,8 +427,7 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
             const bool can_hnsw = ix->has_graph && search_time_ef(ix->cfg, 100) <= wv::HNSW_EF_MAX;
             for (int q = 0; q < nq; ++q) {
                 const uint64_t L = allow_offsets[q + 1] - allow_offsets[q];
-                const bool flat = !can_hnsw || (!ix->cfg.forbid_flat && (int64_t)L < ix->cfg.flat_search_cutoff);
-                if (!flat) {
+                if (!flat_by_len(ix, can_hnsw, L)) {
                     r1.slot[q] = (int)hnsw_q.size();
                     hnsw_q.push_back(q);
                 }
@@ -499,34 +492,17 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
                     // bounded scratch, then SearchByVector(limit 100)
                     HIP_TRY(ix->fi_sel.ensure((size_t)nh * 4));
                     HIP_TRY(hipMemcpyAsync(ix->fi_sel.p, hnsw_q.data(), (size_t)nh * 4, hipMemcpyHostToDevice, s));
-                    const uint64_t words = std::max<uint64_t>(1, (N + 63) / 64);
-                    const size_t rows_cap =
-                        (size_t)std::max<uint64_t>(1, std::min<uint64_t>(65535, (1ull << 30) / (words * 8)));
-                    for (size_t c0 = 0; c0 < (size_t)nh; c0 += rows_cap) {
-                        const int n = (int)std::min(rows_cap, (size_t)nh - c0);
-                        const int32_t* d_sel = ix->fi_sel.as<int32_t>() + c0;
-                        uint64_t ml = 0;
-                        for (int i = 0; i < n; ++i) ml = std::max(ml, off[hnsw_q[c0 + i] + 1] - off[hnsw_q[c0 + i]]);
-                        HIP_TRY(ix->fi_q.ensure((size_t)n * ix->dpad * 4));
-                        HIP_TRY(ix->fi_bits.ensure((size_t)n * words * 8));
-                        HIP_TRY(ix->fi_oid.ensure((size_t)n * 100 * 8));
-                        HIP_TRY(ix->fi_od.ensure((size_t)n * 100 * 4));
-                        HIP_TRY(ix->fi_on.ensure((size_t)n * 4));
-                        HIP_TRY(launch_gather_rows(ix->sbd_q.as<float>(), ix->dpad, d_sel, n, ix->dpad, ix->fi_q.as<float>(),
-                                                   ix->dpad, s));
-                        HIP_TRY(hipMemsetAsync(ix->fi_bits.p, 0, (size_t)n * words * 8, s));
-                        HIP_TRY(wv_launch_ids_to_bits(ix->fi_ids.as<uint32_t>(), ix->fi_off.as<uint64_t>(), d_sel, n, ml,
-                                                      N, words, ix->fi_bits.as<uint64_t>(), s));
-                        rc = search_core(ix, ix->fi_q.as<float>(), n, 100, 0, ix->fi_bits.as<uint64_t>(),
-                                         std::max<uint64_t>(N, 1), words, WV_MODE_HNSW, ix->fi_oid.as<uint64_t>(),
-                                         ix->fi_od.as<float>(), ix->fi_on.as<int32_t>(), s);
-                        if (rc) return rc;
+                    auto keep_r1 = [&](size_t c0, int n, const int32_t*) -> int {
                         HIP_TRY(hipMemcpyAsync(r1.ids.data() + c0 * 100, ix->fi_oid.p, (size_t)n * 100 * 8,
                                                hipMemcpyDeviceToHost, s));
                         HIP_TRY(hipMemcpyAsync(r1.d.data() + c0 * 100, ix->fi_od.p, (size_t)n * 100 * 4,
                                                hipMemcpyDeviceToHost, s));
                         HIP_TRY(hipMemcpyAsync(r1.n.data() + c0, ix->fi_on.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-                    }
+                        return WV_OK;
+                    };
+                    rc = ids_bitmap_route(ix, ix->sbd_q.as<float>(), hnsw_q.data(), ix->fi_sel.as<int32_t>(), (size_t)nh,
+                                          100, 0, WV_MODE_HNSW, off, s, keep_r1);
+                    if (rc) return rc;
                 }
                 HIP_TRY(hipMemcpyAsync(cnt.data() + 3 * (size_t)q0, ix->sbd_cnt.as<unsigned int>() + 3 * (size_t)q0,
                                        (size_t)nqc * 12, hipMemcpyDeviceToHost, s));

@@ -1,13 +1,16 @@
 // wv_index.h -- what the host files of the C ABI share (wv_api.hip,
-// wv_search.hip, wv_distance.hip, wv_build.hip): the index itself and the
-// helpers that more than one of them calls.  Internal: all of it has hidden
-// visibility, the library exports include/wvgpu.h only.
+// wv_search*.hip, wv_distance.hip, wv_build.hip): the index itself and the
+// helpers that more than one of them calls (the search files' own: wv_search.h).
+// Internal: all of it has hidden visibility, the library exports
+// include/wvgpu.h only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <condition_variable>
+#include <cstdlib>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -67,6 +70,26 @@ struct DevBuf {
 // rows of the corpus buffers: whole 128-row tiles of the brute-force passes
 // and whole 256-row tiles of the wide f16 pass (wv_bf_h16w_kernel<.., 128>)
 inline uint64_t align_rows(uint64_t n) { return (n + 255) / 256 * 256; }
+
+// Environment switches.  Read per call: tests flip them between calls of one
+// process.  env_on: set at all (NAME=0 counts as set); env_int: atoi of the
+// value, at least min, or, when unset, dflt as given -- min is not applied to
+// it, so a dflt of 0 under a min >= 1 tells "unset" apart (WV_H16_SAMPLE,
+// WV_HNSW_SIDE_ROWS, WV_HNSW_SPILL_CAP); env_tri: 0 / 1, or -1 when unset or
+// empty.
+inline bool env_on(const char* name) { return std::getenv(name) != nullptr; }
+inline int env_int(const char* name, int dflt, int min = INT_MIN) {
+    const char* e = std::getenv(name);
+    return e ? std::max(min, std::atoi(e)) : dflt;
+}
+inline double env_double(const char* name, double dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atof(e) : dflt;
+}
+inline int env_tri(const char* name) {
+    const char* e = std::getenv(name);
+    return e && *e ? (std::atoi(e) ? 1 : 0) : -1;
+}
 
 }  // namespace wv_host
 
@@ -242,21 +265,6 @@ hipError_t launch_pad_rows(const float* src, uint64_t ld_src, uint64_t n, int D,
 // out[q] = the first k of n_shards sorted lists merged by (dist, id); 128 queries per workgroup
 hipError_t launch_merge_shards(const float* in_d, const uint64_t* in_ids, const int32_t* in_n, int n_shards, int nq,
                                int k, float* out_d, uint64_t* out_ids, int32_t* out_n, hipStream_t s);
-
-// wv_search.hip: the device pipelines, the pinned slots, per-query allow lists given as ids
-int choose_vc_log2(int per_wave_budget_words, int fixed_words, uint64_t n_nodes, int* tbits);
-int search_core(wv_index* ix, const float* d_q, int nq, int k, int ef, const uint64_t* d_allow, uint64_t allow_nbits,
-                uint64_t allow_stride, int mode, uint64_t* d_out_ids, float* d_out_d, int32_t* d_out_n, hipStream_t s);
-int stage_queries(wv_index* ix, const float* q, int nq, const float** d_out, hipStream_t s);
-// dst[r] = src[idx[r]] for n rows (zero past D), one 128-thread workgroup per row
-hipError_t launch_gather_rows(const float* src, int ld_src, const int32_t* idx, int n, int D, float* dst, int ld_dst,
-                              hipStream_t s);
-int slot_reserve(wv_index::HostSlot& sl, size_t need);
-int ids_check_offsets(const std::string& fn, const uint64_t* allow_ids, const uint64_t* allow_offsets, int nq);
-int ids_stage(const std::string& fn, const uint64_t* allow_ids, const uint64_t* allow_offsets, int nq, uint32_t* ids32,
-              uint64_t* off);
-int ids_upload(wv_index* ix, const uint32_t* ids32, const uint64_t* off, int nq, hipStream_t s);
-void ids_chunks(const wv_index* ix, int ns, uint64_t max_len, uint64_t* chunk_len, uint64_t* n_chunks);
 
 }  // namespace wv_host
 

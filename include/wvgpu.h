@@ -266,7 +266,18 @@ int wv_search_by_vector_distance(wv_index *ix, const float *vector, float target
  * read per call: the per-query rounds instead; WV_SBD_PQ_LUT=0|1: the pass
  * evaluates rows directly / from the per-query lookup table wherever it fits,
  * for tests and A/B runs).  A query whose within-target set outgrows
- * WV_SBD_CAP entries takes the per-query wv_search_by_vector_distance. */
+ * WV_SBD_CAP entries takes the per-query wv_search_by_vector_distance.
+ * With wv_index_set_sbd_key_pass on, an index that is not compressed, has
+ * D <= 128 and whose f16 image and scale are current (the state in which its
+ * exact k-NN searches take the f16 key pass) answers the threshold pass of
+ * every query of the batch in two stages: an f16 MFMA filter that keeps the
+ * rows whose key is under a certified per-query bound, then the reference-
+ * order distances of those candidates alone -- the same ids, distance bits
+ * and counts.  A query with more than 2 x WV_SBD_CAP candidates
+ * (WV_SBD_H16_CAND, read per call: another capacity, for tests) is answered
+ * by the scan of before, in the same call.  WV_SBD_H16_BLOCKS (read per
+ * call) caps the corpus segments per query block, for tests and A/B runs.
+ * Follow-ups: D > 128, the Go binding, the switch as the library default. */
 int wv_search_by_vector_distance_batch(wv_index *ix, const float *queries, int nq, const float *target_distances,
                                        int64_t max_limit, const uint64_t *allow_bits, uint64_t allow_nbits,
                                        uint64_t allow_stride_words, uint64_t *out_ids, float *out_dists,
@@ -309,6 +320,22 @@ int wv_last_sbd_ids_stats(wv_index *ix, uint64_t *list_queries, uint64_t *list_i
  * was an HNSW search, queries sent down the per-query path.  A null index
  * returns WV_EINVAL. */
 int wv_last_sbd_stats(wv_index *ix, uint64_t *pass_queries, uint64_t *hnsw_round1_queries, uint64_t *legacy_queries);
+/* The threshold pass of wv_search_by_vector_distance_batch (and of what reaches
+ * it: the batcher's bitmap batches, group members, the mirror) runs as the
+ * f16 MFMA filter + exact stage (on) or as the scan over every row (off, the
+ * default) where the index is eligible: not compressed, D <= 128, f16 image
+ * and scale current.  Elsewhere the setting has no effect; the answers are
+ * the same bits either way.  A null index returns WV_EINVAL.  (Off by
+ * default until callers have measured it on their own batches; a single
+ * query gains the least: profiles/sbd_h16/README.md.) */
+int wv_index_set_sbd_key_pass(wv_index *ix, int on);
+/* The last wv_search_by_vector_distance_batch on the index (nullable
+ * outputs): queries whose threshold pass ran as the f16 filter, the
+ * candidates it found over all of them, and the queries whose candidates
+ * outgrew their lists and were answered by the scan.  All 0 when the filter
+ * did not run.  A null index returns WV_EINVAL. */
+int wv_last_sbd_key_pass_stats(wv_index *ix, uint64_t *key_pass_queries, uint64_t *candidates,
+                               uint64_t *overflow_queries);
 
 /* Batched search of nq queries (row-major [nq][dim]).  ef <= 0 selects
  * searchTimeEF(k).  allow_bits may be NULL, one bitmap shared by the batch

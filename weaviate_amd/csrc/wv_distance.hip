@@ -68,6 +68,118 @@ void sbd_fill(const wv_index* ix, P& sp) {
     sp.cnt = ix->sbd_cnt.as<unsigned int>();
 }
 
+// The f16 threshold filter and its exact stage in place of the scan
+// (wv_sbd_h16.hip): whether this batch may take it, and its launches.
+// Candidates per query: 2 x the list's entries by default.  A query whose
+// within-target set outgrows the list takes the per-query path whatever the
+// filter found, so room past the list only pays for the margin's extra rows;
+// twice the list lets the certificate's margin double the set before the scan
+// is launched again, and its 4-byte ids then take the memory of one of the
+// two 8-byte key buffers.  WV_SBD_H16_CAND (read per call) overrides it.
+bool sbd_h16_ok(const wv_index* ix) {
+    return ix->sbd_key_pass && !ix->pq_on && ix->use_h16 && !ix->h16_wide && ix->h16_sx > 0.f &&
+           std::isfinite(ix->h16_ex) && std::isfinite(ix->maxnorm_host) && ix->n_rows > 0 && ix->n_rows < (1ull << 31);
+}
+int sbd_h16_cand(int cap) {
+    return env_int("WV_SBD_H16_CAND", (int)std::min<int64_t>(2 * (int64_t)cap, 1 << 26), 1);
+}
+
+// sp: the scan's parameters of the same batch (the staged queries, targets,
+// bitmaps, lists and counts); candidates and their counts stay in
+// ix->sbd_cand / ix->sbd_ccnt
+int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s) {
+    const int nq = sp.nq, ns = ix->h16_ns;
+    const uint64_t N = sp.N, ntiles = (N + wv::H_BN - 1) / wv::H_BN;
+    // 64-query blocks for a batch of up to 64, else 512-query blocks
+    const int qw = nq <= 64 ? 1 : wv::SBDH_WAVES, bq = 64 * qw, nqb = (nq + bq - 1) / bq;
+    const size_t qbytes = (size_t)nqb * bq * ns * 16 * 2;
+    const int lists = sp.allow && sp.allow_stride ? nq : 1;
+    HIP_TRY(ix->qimg16.ensure(qbytes));
+    HIP_TRY(ix->qres.ensure((size_t)nq * 4));
+    HIP_TRY(ix->q_nrm2.ensure((size_t)nq * 4));
+    HIP_TRY(ix->qmax_part.ensure((size_t)((nq + 3) / 4) * 4));
+    HIP_TRY(ix->sbd_bound.ensure((size_t)nq * 4));
+    HIP_TRY(ix->sbd_ccnt.ensure((size_t)nq * 4));
+    HIP_TRY(ix->sbd_cand.ensure((size_t)nq * ccap * 4));
+    HIP_TRY(ix->sbd_nelig.ensure((size_t)lists * 4));
+    // the k-NN key pass's operands (run_h16): |q|^2 and the batch's max |q_i|,
+    // s_q, B = f16(s_q b) with its residual, and s |x|^2 for the L2 C-in
+    const float bsign = ix->metric == WV_L2_SQUARED ? -2.f : -1.f;
+    HIP_TRY(wv_launch_qnorm(sp.Q, nq, ix->dim, ix->dpad, ix->metric, ix->q_nrm2.as<float>(), ix->qmax_part.as<float>(),
+                            s));
+    HIP_TRY(hipMemsetAsync(ix->qimg16.p, 0, qbytes, s));
+    HIP_TRY(wv_launch_h16_qscale(ix->qmax_part.as<float>(), (nq + 3) / 4, ix->qmax.as<unsigned int>(), bsign,
+                                 ix->qscale.as<float>(), s));
+    HIP_TRY(wv_launch_h16_rows(sp.Q, ix->dpad, nullptr, nq, ix->dim, ns, bsign, 1.f, ix->qmax.as<unsigned int>(),
+                               ix->qimg16.p, 0, nullptr, ix->qres.as<float>(), 0, s));
+    if (ix->metric == WV_L2_SQUARED)
+        HIP_TRY(wv_launch_h16_xns(ix->xnorm.as<float>(), ntiles * wv::H_BN, ix->h16_sx, ix->qscale.as<float>(),
+                                  ix->xns.as<float>(), s));
+    wv::SbdH16BoundParams bp{};
+    bp.target = sp.target;
+    bp.qnorm = ix->q_nrm2.as<float>();
+    bp.qres = ix->qres.as<float>();
+    bp.qscale = ix->qscale.as<float>();
+    bp.sx = ix->h16_sx;
+    bp.xnorm_max = ix->maxnorm_host;
+    bp.ex_max = ix->h16_ex;
+    bp.nq = nq;
+    bp.metric = ix->metric;
+    bp.D = ix->dim;
+    bp.ccap = ccap;
+    bp.bound = ix->sbd_bound.as<float>();
+    bp.ccnt = ix->sbd_ccnt.as<unsigned int>();
+    HIP_TRY(wv_launch_sbd_h16_bound(&bp, s));
+    HIP_TRY(hipMemsetAsync(ix->sbd_nelig.p, 0, (size_t)lists * 4, s));
+    HIP_TRY(wv_launch_sbd_h16_count(sp.excl, sp.allow, sp.allow_nbits, sp.allow_stride, N, nq,
+                                    ix->sbd_nelig.as<unsigned int>(), s));
+    wv::SbdH16Params hp{};
+    hp.X = ix->ximg16.p;
+    hp.Q = ix->qimg16.p;
+    hp.xns = ix->xns.as<float>();
+    hp.bound = bp.bound;
+    hp.excl = sp.excl;
+    hp.allow = sp.allow;
+    hp.excl_nbits = sp.excl_nbits;
+    hp.allow_nbits = sp.allow_nbits;
+    hp.allow_stride = sp.allow_stride;
+    hp.N = N;
+    hp.nq = nq;
+    hp.metric = ix->metric;
+    hp.ns = ns;
+    hp.qwaves = qw;
+    hp.n_qblocks = nqb;
+    // segments: two workgroups per CU over the query blocks, whole stages each
+    // (WV_SBD_H16_BLOCKS, read per call, caps the segments per query block)
+    const uint64_t tps = qw == 1 ? 4 : 2, stages = (ntiles + tps - 1) / tps;
+    uint64_t n_seg = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 2 / (uint64_t)nqb);
+    n_seg = std::min<uint64_t>(n_seg, (uint64_t)env_int("WV_SBD_H16_BLOCKS", INT_MAX, 1));
+    n_seg = std::min(n_seg, stages);
+    hp.ntiles = (uint32_t)ntiles;
+    hp.tiles_per_seg = (uint32_t)((stages + n_seg - 1) / n_seg * tps);
+    hp.n_seg = (int)((ntiles + hp.tiles_per_seg - 1) / hp.tiles_per_seg);
+    hp.cand = ix->sbd_cand.as<uint32_t>();
+    hp.ccnt = bp.ccnt;
+    hp.ccap = ccap;
+    HIP_TRY(wv_launch_sbd_h16(&hp, s));
+    // the exact stage: sbd_ids_kernel over the candidate lists
+    wv::SbdIdsParams ip{};
+    sbd_fill(ix, ip);
+    ip.ids = hp.cand;
+    ip.n_rows = N;
+    ip.chunk_len = 1024;
+    ip.n_chunks = (int)std::min<int64_t>(((int64_t)ccap + 1023) / 1024, 65535);
+    ip.nq = nq;
+    ip.cand_cnt = hp.ccnt;
+    ip.n_elig = ix->sbd_nelig.as<unsigned int>();
+    ip.cand_cap = ccap;
+    ip.key_cap = sp.cap;
+    ip.n_elig_stride = lists > 1 ? 1 : 0;
+    if ((int64_t)ip.n_chunks * 1024 < ccap) return fail(WV_EINVAL, "WV_SBD_H16_CAND: too many candidates per query");
+    HIP_TRY(wv_launch_sbd_ids(&ip, s));
+    return WV_OK;
+}
+
 // the search.go:90-158 loop over an exact sorted list (from round r0: 1 when
 // round 1 is exact too, 2 after an HNSW round 1): the end of the kept prefix
 int64_t sbd_exact_rounds(int r0, int64_t Qn, int64_t A, int64_t n, int64_t max_limit) {
@@ -173,6 +285,7 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
     {
         std::lock_guard<std::mutex> g(ix->mu);
         ix->sbd_pass_q = ix->sbd_hnsw_q = 0;
+        ix->sbd_kp_q = ix->sbd_kp_cand = ix->sbd_kp_over = 0;
         ix->sbd_legacy_q = (uint64_t)nq;
         if (ix->pq_on && !sbd_pq_enabled()) {
             for (int q = 0; q < nq; ++q) legacy.push_back(q);
@@ -226,7 +339,17 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
             // every query's threshold pass (its queries staged first: round
             // 1's search restages q_in)
             const float* dq = nullptr;
-            bool passed = false;
+            bool passed = false, keyed = false;   // keyed: the f16 filter ran in place of the scan
+            wv::SbdParams scan_p{};               // the scan's parameters, kept for the filter's overflow
+            int ccap = 0;
+            // ~4 blocks per CU over the scanned queries, whole 4-wave steps of 256 rows
+            auto scan_rows = [&](uint64_t N, int nqs) {
+                const uint64_t target_blocks = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 4 / (uint64_t)nqs);
+                uint64_t rpb = std::max<uint64_t>(4096, (N + target_blocks - 1) / target_blocks);
+                rpb = (rpb + 255) / 256 * 256;
+                while ((N + rpb - 1) / rpb > 65535) rpb *= 2;
+                return rpb;
+            };
             auto launch_pass = [&]() -> int {
                 int rc = stage_queries(ix, queries, nq, &dq, s);
                 if (rc) return rc;
@@ -246,11 +369,7 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 sp.allow_stride = allow_stride_words;
                 sp.N = ix->n_rows;
                 sp.nq = nq;
-                // ~4 blocks per CU over the batch, whole 4-wave steps of 256 rows
-                const uint64_t target_blocks = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 4 / (uint64_t)nq);
-                sp.rows_per_block = std::max<uint64_t>(4096, (sp.N + target_blocks - 1) / target_blocks);
-                sp.rows_per_block = (sp.rows_per_block + 255) / 256 * 256;
-                while ((sp.N + sp.rows_per_block - 1) / sp.rows_per_block > 65535) sp.rows_per_block *= 2;
+                sp.rows_per_block = scan_rows(sp.N, nq);
                 sp.cap = cap;
                 if (ix->pq_on) {
                     wv::SbdPqParams pp{};
@@ -270,6 +389,11 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                     }
                     pp.s = sp;
                     HIP_TRY(wv_launch_sbd_pq_scan(&pp, s));
+                } else if (sbd_h16_ok(ix)) {
+                    ccap = sbd_h16_cand(cap);
+                    scan_p = sp;
+                    if (int rc = sbd_h16_pass(ix, sp, ccap, s)) return rc;
+                    keyed = true;
                 } else {
                     HIP_TRY(wv_launch_sbd_scan(&sp, s));
                 }
@@ -321,9 +445,36 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 rc = launch_r1();
                 if (rc) return rc;
             }
+            std::vector<unsigned int> ccnt(keyed ? nq : 0);
             if (passed)
                 HIP_TRY(hipMemcpyAsync(cnt.data(), ix->sbd_cnt.p, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
+            if (keyed) HIP_TRY(hipMemcpyAsync(ccnt.data(), ix->sbd_ccnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
+            if (keyed) {
+                // the queries whose candidates outgrew their lists: their
+                // counts cleared, the scan over just them, the sort again
+                std::vector<int> over;
+                for (int q = 0; q < nq; ++q) {
+                    ix->sbd_kp_cand += ccnt[q];
+                    if (ccnt[q] > (unsigned int)ccap) over.push_back(q);
+                }
+                ix->sbd_kp_q = (uint64_t)nq;
+                ix->sbd_kp_over = over.size();
+                if (!over.empty()) {
+                    HIP_TRY(ix->sbd_qidx.ensure(over.size() * 4));
+                    HIP_TRY(hipMemcpyAsync(ix->sbd_qidx.p, over.data(), over.size() * 4, hipMemcpyHostToDevice, s));
+                    for (int q : over) HIP_TRY(hipMemsetAsync(ix->sbd_cnt.as<unsigned int>() + 3 * (size_t)q, 0, 12, s));
+                    scan_p.qidx = ix->sbd_qidx.as<int>();
+                    scan_p.nq = (int)over.size();
+                    scan_p.rows_per_block = scan_rows(scan_p.N, scan_p.nq);
+                    HIP_TRY(wv_launch_sbd_scan(&scan_p, s));
+                    HIP_TRY(wv_sbd_sort(ix->sbd_keys.as<unsigned long long>(), ix->sbd_tmp.as<unsigned long long>(),
+                                        ix->sbd_cnt.as<unsigned int>(), nq, cap, ix->sbd_off.as<int>(), &ix->sbd_scr,
+                                        &ix->sbd_scr_cap, s));
+                    HIP_TRY(hipMemcpyAsync(cnt.data(), ix->sbd_cnt.p, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                }
+            }
             // the sorted lists, as far as the rounds keep them (and the caller
             // takes them)
             std::vector<int64_t> need(nq, 0);
@@ -571,6 +722,23 @@ int wv_last_sbd_ids_stats(wv_index* ix, uint64_t* list_queries, uint64_t* list_i
     if (list_ids) *list_ids = ix->sbd_ids_list_ids;
     if (hnsw_round1_queries) *hnsw_round1_queries = ix->sbd_ids_hnsw_q;
     if (legacy_queries) *legacy_queries = ix->sbd_ids_legacy_q;
+    return WV_OK;
+}
+
+int wv_index_set_sbd_key_pass(wv_index* ix, int on) {
+    if (!ix) return fail(WV_EINVAL, "wv_index_set_sbd_key_pass: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->sbd_key_pass = on != 0;
+    return WV_OK;
+}
+
+int wv_last_sbd_key_pass_stats(wv_index* ix, uint64_t* key_pass_queries, uint64_t* candidates,
+                               uint64_t* overflow_queries) {
+    if (check(ix)) return fail(WV_EINVAL, "wv_last_sbd_key_pass_stats: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (key_pass_queries) *key_pass_queries = ix->sbd_kp_q;
+    if (candidates) *candidates = ix->sbd_kp_cand;
+    if (overflow_queries) *overflow_queries = ix->sbd_kp_over;
     return WV_OK;
 }
 

@@ -152,6 +152,12 @@ struct wv_index {
     DevBuf sbd_seg;         // (the id-list route) a chunk's segment starts, lengths and ends
     uint64_t sbd_ids_list_q = 0, sbd_ids_list_ids = 0, sbd_ids_hnsw_q = 0, sbd_ids_legacy_q = 0;   // the last call's routes
     uint64_t sbd_pass_q = 0, sbd_hnsw_q = 0, sbd_legacy_q = 0;   // the same of the last bitmap-route batch
+    // the f16 threshold filter of the bitmap-route batch (wv_sbd_h16.hip,
+    // wv_index_set_sbd_key_pass): bounds, candidate lists and counts, the
+    // bitmaps' eligible-row counts, the overflowed queries; the last call's stats
+    bool sbd_key_pass = false;
+    DevBuf sbd_bound, sbd_cand, sbd_ccnt, sbd_nelig, sbd_qidx;
+    uint64_t sbd_kp_q = 0, sbd_kp_cand = 0, sbd_kp_over = 0;
     void* sbd_scr = nullptr;
     size_t sbd_scr_cap = 0;
     DevBuf scan_d, scan_i, sort_d, sort_i, sort_tmp;

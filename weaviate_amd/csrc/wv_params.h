@@ -405,6 +405,7 @@ struct SbdParams {
     int cap;                  // list entries per query
     unsigned long long* keys; // [nq][cap]: (orderable d) << 32 | row
     unsigned int* cnt;        // [nq][3]: |Q|, A (d <= target), n (rows searchable)
+    const int* qidx;          // nullable: grid column i scans query qidx[i] of the batch, nq of them (null: query i)
 };
 
 // The threshold pass over per-query allow lists given as ids (wv_sbd.hip,
@@ -426,6 +427,49 @@ struct SbdIdsParams {
     int D, dpad, ldx, metric;
     unsigned long long* keys; // [sum of seg_cap]: (orderable d) << 32 | row
     unsigned int* cnt;        // [batch][3]: |Q|, A (d <= target), n (rows searchable)
+    // The candidate form (the exact stage of the f16 threshold filter,
+    // wv_sbd_h16.hip; cand_cnt non-null): query q's list is ids[q cand_cap ..
+    // + cand_cnt[q]), its keys go to keys[q key_cap ..), and off, seg_beg and
+    // seg_cap are not read.  A query whose count exceeds cand_cap is skipped
+    // (its counts stay zero: the scan answers it).  n is not counted from the
+    // list: n_elig[q] (n_elig_stride 1) or n_elig[0] (0) is added once.
+    const unsigned int* cand_cnt;
+    const unsigned int* n_elig;
+    int cand_cap, key_cap, n_elig_stride;
+};
+
+// The f16 MFMA threshold filter of the distance search (wv_sbd_h16.hip): per
+// query, the ids of the eligible rows whose f16 key is under the query's bound
+// -- a superset of the rows within the target distance (h16_eps).
+constexpr int SBDH_WAVES = 8;   // waves per workgroup
+struct SbdH16Params {
+    const void* X;            // corpus image (h16_index), whole 64-row tiles
+    const void* Q;            // query image, zero padded to whole query blocks
+    const float* xns;         // s |x|^2 per row (L2 only)
+    const float* bound;       // [nq] key bound in scaled units (-inf: nothing passes)
+    const uint64_t* excl;     // tombstones, nil nodes, missing rows
+    const uint64_t* allow;    // nullable; [nq][allow_stride] or shared (stride 0)
+    uint64_t excl_nbits, allow_nbits, allow_stride, N;
+    int nq, metric, ns;
+    int qwaves;               // waves across the queries: 1 (64-query blocks) or SBDH_WAVES (512)
+    int n_qblocks, n_seg;     // grid: corpus segments x query blocks
+    uint32_t ntiles, tiles_per_seg;   // 64-row tiles of the corpus; per segment (whole stages)
+    uint32_t* cand;           // [nq][ccap] row ids
+    unsigned int* ccnt;       // [nq] candidates found (counts past ccap)
+    int ccap;
+};
+
+// Its prologue: the per-query bound from the target and the certificate, and
+// the candidate counts' start (0, or ccap + 1 where only the scan can answer)
+struct SbdH16BoundParams {
+    const float* target;      // [nq]
+    const float* qnorm;       // |q|^2 (L2) or |q|
+    const float* qres;        // [nq] query image residual
+    const float* qscale;      // device scalar s_q
+    float sx, xnorm_max, ex_max;
+    int nq, metric, D, ccap;
+    float* bound;             // [nq]
+    unsigned int* ccnt;       // [nq]
 };
 
 // Flat search over per-query id lists (wv_flat_ids.hip; flat_search.go:24-58):

@@ -39,9 +39,9 @@ __global__ __launch_bounds__(256) void sbd_scan_kernel(SbdParams p) {
     __shared__ float qv[1024];
     __shared__ uint32_t ids[4][64];
     __shared__ float ds[4][64];
-    const int q = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (q >= p.nq || p.dpad > 1024) return;
+    if ((int)blockIdx.x >= p.nq || p.dpad > 1024) return;
+    const int q = p.qidx ? p.qidx[blockIdx.x] : (int)blockIdx.x;
     for (int i = threadIdx.x; i < p.dpad; i += 256) qv[i] = p.Q[(uint64_t)q * p.dpad + i];
     __syncthreads();
     const double t = (double)p.target[q];
@@ -96,7 +96,10 @@ __global__ void sbd_offsets_kernel(const unsigned int* cnt, int nq, int cap, int
 // walks its chunk 64 ids a step as flat_ids_kernel does (ids past the rows and
 // excluded rows dropped, survivors compacted into its LDS slots) and appends
 // as sbd_scan_kernel does, into the query's own segment of seg_cap keys.
-template <int METRIC>
+// CAND: the exact stage of the f16 threshold filter (wv_sbd_h16.hip) -- the
+// same walk over the query's candidate list (SbdIdsParams: the candidate
+// form), with n taken from the bitmaps' count instead of the list.
+template <int METRIC, bool CAND = false>
 __global__ __launch_bounds__(256) void sbd_ids_kernel(SbdIdsParams p) {
     extern __shared__ __attribute__((aligned(16))) char sbd_smem[];
     uint32_t* sid = reinterpret_cast<uint32_t*>(sbd_smem);        // [4][64]
@@ -106,16 +109,31 @@ __global__ __launch_bounds__(256) void sbd_ids_kernel(SbdIdsParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (qi >= p.nq) return;
     const int q = p.q0 + qi;
+    unsigned int seg_cap;
+    unsigned long long* keys;
+    uint64_t l_beg, l_end;
+    if (CAND) {
+        const unsigned int nc = p.cand_cnt[q];
+        if (nc > (unsigned int)p.cand_cap) return;   // (overflowed: left to the scan)
+        seg_cap = (unsigned int)p.key_cap;
+        keys = p.keys + (uint64_t)q * p.key_cap;
+        l_beg = (uint64_t)q * p.cand_cap;
+        l_end = l_beg + nc;
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(p.cnt + 3 * q + 2, p.n_elig[p.n_elig_stride ? q : 0]);
+        if (l_beg + (uint64_t)blockIdx.y * p.chunk_len >= l_end) return;   // (most chunks of most lists are empty)
+    } else {
+        seg_cap = (unsigned int)p.seg_cap[qi];
+        keys = p.keys + p.seg_beg[qi];
+        l_beg = p.off[q];
+        l_end = p.off[q + 1];
+    }
     for (int i = threadIdx.x; i < p.dpad; i += 256) qv[i] = p.Q[(uint64_t)q * p.dpad + i];
     __syncthreads();
     sid += 64 * wave;
     sds += 64 * wave;
     const float tf = p.target[q];
     const double t = (double)tf;
-    const unsigned int seg_cap = (unsigned int)p.seg_cap[qi];
-    unsigned long long* keys = p.keys + p.seg_beg[qi];
-    const uint64_t l_end = p.off[q + 1];
-    uint64_t beg = p.off[q] + (uint64_t)blockIdx.y * p.chunk_len;
+    uint64_t beg = l_beg + (uint64_t)blockIdx.y * p.chunk_len;
     if (beg > l_end) beg = l_end;
     const uint64_t end = l_end - beg > p.chunk_len ? beg + p.chunk_len : l_end;
     unsigned int n_a = 0, n_ok = 0;   // (lane 0's running counts)
@@ -156,7 +174,7 @@ __global__ __launch_bounds__(256) void sbd_ids_kernel(SbdIdsParams p) {
         __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0 && n_a) atomicAdd(p.cnt + 3 * q + 1, n_a);
-    if (lane == 0 && n_ok) atomicAdd(p.cnt + 3 * q + 2, n_ok);
+    if (!CAND && lane == 0 && n_ok) atomicAdd(p.cnt + 3 * q + 2, n_ok);
 }
 
 // segment ends of the list route's sort: seg_beg[i] + min(|Q|, seg_cap[i])
@@ -178,6 +196,13 @@ hipError_t wv_launch_sbd_ids(const wv::SbdIdsParams* p, hipStream_t s) {
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)p->nq, (unsigned)p->n_chunks);
     const size_t lds = 8 * 64 * 4 + (size_t)p->dpad * 4;
+    if (p->cand_cnt) {
+        if (!p->n_elig || p->cand_cap < 1 || p->key_cap < 1) return hipErrorInvalidValue;
+        if (p->metric == WV_METRIC_L2) hipLaunchKernelGGL((wv::sbd_ids_kernel<WV_METRIC_L2, true>), grid, dim3(256), lds, s, *p);
+        else if (p->metric == WV_METRIC_DOT) hipLaunchKernelGGL((wv::sbd_ids_kernel<WV_METRIC_DOT, true>), grid, dim3(256), lds, s, *p);
+        else hipLaunchKernelGGL((wv::sbd_ids_kernel<WV_METRIC_COSINE, true>), grid, dim3(256), lds, s, *p);
+        return hipGetLastError();
+    }
     if (p->metric == WV_METRIC_L2) hipLaunchKernelGGL(wv::sbd_ids_kernel<WV_METRIC_L2>, grid, dim3(256), lds, s, *p);
     else if (p->metric == WV_METRIC_DOT) hipLaunchKernelGGL(wv::sbd_ids_kernel<WV_METRIC_DOT>, grid, dim3(256), lds, s, *p);
     else hipLaunchKernelGGL(wv::sbd_ids_kernel<WV_METRIC_COSINE>, grid, dim3(256), lds, s, *p);

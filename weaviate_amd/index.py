@@ -415,6 +415,19 @@ class GPUVectorIndex:
         check(lib().wv_last_sbd_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"pass_queries": a.value, "hnsw_round1_queries": b.value, "legacy_queries": c.value}
 
+    def set_sbd_key_pass(self, on: bool = True):
+        """search_by_vector_distance_batch answers its threshold pass with the
+        f16 MFMA filter + exact stage (on) or the scan over every row (off,
+        the default) on an uncompressed index with D <= 128.  Same answers."""
+        check(lib().wv_index_set_sbd_key_pass(self._h, int(on)))
+
+    def last_sbd_key_pass_stats(self):
+        """The last search_by_vector_distance_batch: queries the f16 filter
+        served, the candidates it found, queries it handed back to the scan."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().wv_last_sbd_key_pass_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"key_pass_queries": a.value, "candidates": b.value, "overflow_queries": c.value}
+
     def search_batch(self, queries, k: int, ef: int = 0, allow=None, mode: str = "auto"):
         """Batched search: (ids [nq,k] uint64, dists [nq,k] f32, n [nq] i32)."""
         qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)

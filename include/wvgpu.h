@@ -277,7 +277,11 @@ int wv_search_by_vector_distance(wv_index *ix, const float *vector, float target
  * (WV_SBD_H16_CAND, read per call: another capacity, for tests) is answered
  * by the scan of before, in the same call.  WV_SBD_H16_BLOCKS (read per
  * call) caps the corpus segments per query block, for tests and A/B runs.
- * Follow-ups: D > 128, the Go binding, the switch as the library default. */
+ * With wv_index_set_sbd_wide_key_pass on, the same holds for an index with
+ * 128 < D <= 1024: its filter streams both operands through LDS over the wide
+ * f16 image (256-row tiles; 256-query blocks, 64-query blocks for batches of
+ * up to 64), with the same bound, candidate capacity, overflow route and
+ * switches.  Follow-ups: the Go binding, the switches as the library default. */
 int wv_search_by_vector_distance_batch(wv_index *ix, const float *queries, int nq, const float *target_distances,
                                        int64_t max_limit, const uint64_t *allow_bits, uint64_t allow_nbits,
                                        uint64_t allow_stride_words, uint64_t *out_ids, float *out_dists,
@@ -329,6 +333,16 @@ int wv_last_sbd_stats(wv_index *ix, uint64_t *pass_queries, uint64_t *hnsw_round
  * default until callers have measured it on their own batches; a single
  * query gains the least: profiles/sbd_h16/README.md.) */
 int wv_index_set_sbd_key_pass(wv_index *ix, int on);
+/* The same switch for vectors of 128 < D <= 1024, whose f16 image has the wide
+ * layout: on, the threshold pass runs as the wide f16 MFMA filter (both
+ * operands streamed through LDS) + exact stage where the index is eligible:
+ * not compressed, 128 < D <= 1024, f16 image and scale current (finite
+ * certificates, a positive scale, fewer than 2^31 rows).  Elsewhere -- an
+ * index with D <= 128 included, which wv_index_set_sbd_key_pass governs -- the
+ * setting has no effect; the answers are the same bits either way.  A null
+ * index returns WV_EINVAL.  (Off by default until callers have measured it on
+ * their own batches: profiles/sbd_h16w/README.md.) */
+int wv_index_set_sbd_wide_key_pass(wv_index *ix, int on);
 /* The last wv_search_by_vector_distance_batch on the index (nullable
  * outputs): queries whose threshold pass ran as the f16 filter, the
  * candidates it found over all of them, and the queries whose candidates

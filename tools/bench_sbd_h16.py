@@ -13,9 +13,12 @@ minimum, maximum and inter-quartile range (the run-to-run spread), the mean
 certificate's margin is), and a fingerprint of the answers to compare
 processes.  --mode off leaves the switch alone; WV_LIBPATH names another build
 (a parent build has no switch: only --mode off runs there), and a driver
-alternates processes of the two builds.
+alternates processes of the two builds.  --dim above 128 with --wide measures
+the wide filter (wv_index_set_sbd_wide_key_pass, wv_sbd_h16w.hip) instead;
+--metric picks l2-squared (the default), dot or cosine-dot.
 
     python tools/bench_sbd_h16.py --mode on --out profiles/sbd_h16/new_on.jsonl
+    python tools/bench_sbd_h16.py --dim 768 --metric dot --wide --mode on --out profiles/sbd_h16w/new_on.jsonl
 """
 import argparse
 import ctypes as C
@@ -51,6 +54,8 @@ def main():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--nq", type=int, nargs="+", default=[1, 64, 1024])
     ap.add_argument("--within", type=int, nargs="+", default=[100, 5000])
+    ap.add_argument("--metric", choices=["l2-squared", "dot", "cosine-dot"], default="l2-squared")
+    ap.add_argument("--wide", action="store_true", help="--mode on sets wv_index_set_sbd_wide_key_pass (D > 128)")
     ap.add_argument("--mode", choices=["on", "off"], default="on")
     ap.add_argument("--steps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -59,12 +64,13 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import synth
+    switch = "wv_index_set_sbd_wide_key_pass" if a.wide else "wv_index_set_sbd_key_pass"
     has_switch = "wv_index_set_sbd_key_pass" in _lib.SIGNATURES
-    if a.mode == "on" and not has_switch:
-        raise SystemExit("this build has no wv_index_set_sbd_key_pass: only --mode off runs")
+    if a.mode == "on" and switch not in _lib.SIGNATURES:
+        raise SystemExit(f"this build has no {switch}: only --mode off runs")
     lib = W.lib()
     nq_max = max(a.nq)
-    ix = W.GPUVectorIndex(a.dim, "l2-squared", capacity=a.n)
+    ix = W.GPUVectorIndex(a.dim, a.metric, capacity=a.n)
     t = torch.empty((a.n, a.dim), dtype=torch.float32, device="cuda")
     synth.fill("gauss", 1, 0, t)
     torch.cuda.synchronize()
@@ -73,7 +79,12 @@ def main():
     synth.fill("gauss", 2, 0, tq)
     qs = np.ascontiguousarray(tq.cpu().numpy())
     sample = t[torch.randperm(a.n, device="cuda", generator=torch.Generator("cuda").manual_seed(3))[:100_000]]
-    ds = torch.cdist(tq, sample).square_()   # [nq_max, 100k]
+    if a.metric == "l2-squared":
+        ds = torch.cdist(tq, sample).square_()   # [nq_max, 100k]
+    elif a.metric == "dot":
+        ds = -(tq @ sample.T)
+    else:
+        ds = 1.0 - torch.nn.functional.normalize(tq, dim=1) @ torch.nn.functional.normalize(sample, dim=1).T
     targets = {}
     for w in a.within:
         if w <= 256:
@@ -84,7 +95,7 @@ def main():
             targets[w] = np.ascontiguousarray(ds.kthvalue(k, dim=1).values.cpu().numpy().astype(np.float32))
     del t, sample, ds
     if a.mode == "on":
-        ix.set_sbd_key_pass(True)
+        (ix.set_sbd_wide_key_pass if a.wide else ix.set_sbd_key_pass)(True)
     out = None
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -108,7 +119,8 @@ def main():
                     ms.append((time.perf_counter() - t0) * 1e3)
             q1, med, q3 = np.percentile(ms, [25, 50, 75])
             m = np.minimum(on, a.cap)
-            rec = {"label": a.label, "mode": a.mode, "n": a.n, "dim": a.dim, "nq": nq, "within": w,
+            rec = {"label": a.label, "mode": a.mode, "n": a.n, "dim": a.dim, "metric": a.metric, "wide": a.wide,
+                   "nq": nq, "within": w,
                    "steps": a.steps, "warmup": a.warmup, "ms_median": float(med), "ms_min": float(min(ms)),
                    "ms_max": float(max(ms)), "ms_iqr": float(q3 - q1), "results_median": float(np.median(on)),
                    "results_mean": float(on.mean()),

@@ -105,6 +105,7 @@ SIGNATURES = {
     "wv_last_sbd_ids_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
     "wv_last_sbd_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "wv_index_set_sbd_key_pass": (C.c_int, [_vp, C.c_int]),
+    "wv_index_set_sbd_wide_key_pass": (C.c_int, [_vp, C.c_int]),
     "wv_last_sbd_key_pass_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "wv_search_batch": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp,
                                   _vp]),

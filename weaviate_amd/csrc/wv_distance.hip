@@ -76,8 +76,9 @@ void sbd_fill(const wv_index* ix, P& sp) {
 // twice the list lets the certificate's margin double the set before the scan
 // is launched again, and its 4-byte ids then take the memory of one of the
 // two 8-byte key buffers.  WV_SBD_H16_CAND (read per call) overrides it.
+// The wide image (D > 128, wv_sbd_h16w.hip) has a switch of its own.
 bool sbd_h16_ok(const wv_index* ix) {
-    return ix->sbd_key_pass && !ix->pq_on && ix->use_h16 && !ix->h16_wide && ix->h16_sx > 0.f &&
+    return (ix->h16_wide ? ix->sbd_wide_key_pass : ix->sbd_key_pass) && !ix->pq_on && ix->use_h16 && ix->h16_sx > 0.f &&
            std::isfinite(ix->h16_ex) && std::isfinite(ix->maxnorm_host) && ix->n_rows > 0 && ix->n_rows < (1ull << 31);
 }
 int sbd_h16_cand(int cap) {
@@ -89,9 +90,11 @@ int sbd_h16_cand(int cap) {
 // ix->sbd_cand / ix->sbd_ccnt
 int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s) {
     const int nq = sp.nq, ns = ix->h16_ns;
-    const uint64_t N = sp.N, ntiles = (N + wv::H_BN - 1) / wv::H_BN;
-    // 64-query blocks for a batch of up to 64, else 512-query blocks
-    const int qw = nq <= 64 ? 1 : wv::SBDH_WAVES, bq = 64 * qw, nqb = (nq + bq - 1) / bq;
+    const bool wd = ix->h16_wide;   // D > 128: sbd_h16w_kernel over 256-row tiles
+    const uint64_t tile_rows = wd ? wv::HW_BN : wv::H_BN;
+    const uint64_t N = sp.N, ntiles = (N + tile_rows - 1) / tile_rows;
+    // 64-query blocks for a batch of up to 64, else 512-query blocks (D > 128: 256)
+    const int qw = nq <= 64 ? 1 : wv::SBDH_WAVES, bq = nq <= 64 ? 64 : wd ? wv::HW_BQ : 512, nqb = (nq + bq - 1) / bq;
     const size_t qbytes = (size_t)nqb * bq * ns * 16 * 2;
     const int lists = sp.allow && sp.allow_stride ? nq : 1;
     HIP_TRY(ix->qimg16.ensure(qbytes));
@@ -113,7 +116,7 @@ int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s)
     HIP_TRY(wv_launch_h16_rows(sp.Q, ix->dpad, nullptr, nq, ix->dim, ns, bsign, 1.f, ix->qmax.as<unsigned int>(),
                                ix->qimg16.p, 0, nullptr, ix->qres.as<float>(), 0, s));
     if (ix->metric == WV_L2_SQUARED)
-        HIP_TRY(wv_launch_h16_xns(ix->xnorm.as<float>(), ntiles * wv::H_BN, ix->h16_sx, ix->qscale.as<float>(),
+        HIP_TRY(wv_launch_h16_xns(ix->xnorm.as<float>(), ntiles * tile_rows, ix->h16_sx, ix->qscale.as<float>(),
                                   ix->xns.as<float>(), s));
     wv::SbdH16BoundParams bp{};
     bp.target = sp.target;
@@ -133,44 +136,75 @@ int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s)
     HIP_TRY(hipMemsetAsync(ix->sbd_nelig.p, 0, (size_t)lists * 4, s));
     HIP_TRY(wv_launch_sbd_h16_count(sp.excl, sp.allow, sp.allow_nbits, sp.allow_stride, N, nq,
                                     ix->sbd_nelig.as<unsigned int>(), s));
-    wv::SbdH16Params hp{};
-    hp.X = ix->ximg16.p;
-    hp.Q = ix->qimg16.p;
-    hp.xns = ix->xns.as<float>();
-    hp.bound = bp.bound;
-    hp.excl = sp.excl;
-    hp.allow = sp.allow;
-    hp.excl_nbits = sp.excl_nbits;
-    hp.allow_nbits = sp.allow_nbits;
-    hp.allow_stride = sp.allow_stride;
-    hp.N = N;
-    hp.nq = nq;
-    hp.metric = ix->metric;
-    hp.ns = ns;
-    hp.qwaves = qw;
-    hp.n_qblocks = nqb;
-    // segments: two workgroups per CU over the query blocks, whole stages each
-    // (WV_SBD_H16_BLOCKS, read per call, caps the segments per query block)
-    const uint64_t tps = qw == 1 ? 4 : 2, stages = (ntiles + tps - 1) / tps;
-    uint64_t n_seg = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 2 / (uint64_t)nqb);
-    n_seg = std::min<uint64_t>(n_seg, (uint64_t)env_int("WV_SBD_H16_BLOCKS", INT_MAX, 1));
-    n_seg = std::min(n_seg, stages);
-    hp.ntiles = (uint32_t)ntiles;
-    hp.tiles_per_seg = (uint32_t)((stages + n_seg - 1) / n_seg * tps);
-    hp.n_seg = (int)((ntiles + hp.tiles_per_seg - 1) / hp.tiles_per_seg);
-    hp.cand = ix->sbd_cand.as<uint32_t>();
-    hp.ccnt = bp.ccnt;
-    hp.ccap = ccap;
-    HIP_TRY(wv_launch_sbd_h16(&hp, s));
+    const uint64_t seg_cap = (uint64_t)env_int("WV_SBD_H16_BLOCKS", INT_MAX, 1);
+    uint32_t* cand = ix->sbd_cand.as<uint32_t>();
+    if (wd) {
+        wv::SbdH16WParams wp{};
+        wp.X = ix->ximg16.p;
+        wp.Q = ix->qimg16.p;
+        wp.xns = ix->xns.as<float>();
+        wp.bound = bp.bound;
+        wp.excl = sp.excl;
+        wp.allow = sp.allow;
+        wp.excl_nbits = sp.excl_nbits;
+        wp.allow_nbits = sp.allow_nbits;
+        wp.allow_stride = sp.allow_stride;
+        wp.N = N;
+        wp.nq = nq;
+        wp.metric = ix->metric;
+        wp.ns = ns;
+        wp.qblock = bq;
+        wp.n_qblocks = nqb;
+        // segments of whole tiles: one workgroup per CU over the query blocks
+        // (96 KiB of LDS each), two at 64-query blocks (60 KiB)
+        uint64_t n_seg = std::max<uint64_t>(1, (uint64_t)ix->n_cus * (bq == 64 ? 2 : 1) / (uint64_t)nqb);
+        n_seg = std::min(std::min(n_seg, seg_cap), ntiles);
+        wp.ntiles = (uint32_t)ntiles;
+        wp.tiles_per_seg = (uint32_t)((ntiles + n_seg - 1) / n_seg);
+        wp.n_seg = (int)((ntiles + wp.tiles_per_seg - 1) / wp.tiles_per_seg);
+        wp.cand = cand;
+        wp.ccnt = bp.ccnt;
+        wp.ccap = ccap;
+        HIP_TRY(wv_launch_sbd_h16w(&wp, s));
+    } else {
+        wv::SbdH16Params hp{};
+        hp.X = ix->ximg16.p;
+        hp.Q = ix->qimg16.p;
+        hp.xns = ix->xns.as<float>();
+        hp.bound = bp.bound;
+        hp.excl = sp.excl;
+        hp.allow = sp.allow;
+        hp.excl_nbits = sp.excl_nbits;
+        hp.allow_nbits = sp.allow_nbits;
+        hp.allow_stride = sp.allow_stride;
+        hp.N = N;
+        hp.nq = nq;
+        hp.metric = ix->metric;
+        hp.ns = ns;
+        hp.qwaves = qw;
+        hp.n_qblocks = nqb;
+        // segments: two workgroups per CU over the query blocks, whole stages each
+        // (WV_SBD_H16_BLOCKS, read per call, caps the segments per query block)
+        const uint64_t tps = qw == 1 ? 4 : 2, stages = (ntiles + tps - 1) / tps;
+        uint64_t n_seg = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 2 / (uint64_t)nqb);
+        n_seg = std::min(std::min(n_seg, seg_cap), stages);
+        hp.ntiles = (uint32_t)ntiles;
+        hp.tiles_per_seg = (uint32_t)((stages + n_seg - 1) / n_seg * tps);
+        hp.n_seg = (int)((ntiles + hp.tiles_per_seg - 1) / hp.tiles_per_seg);
+        hp.cand = cand;
+        hp.ccnt = bp.ccnt;
+        hp.ccap = ccap;
+        HIP_TRY(wv_launch_sbd_h16(&hp, s));
+    }
     // the exact stage: sbd_ids_kernel over the candidate lists
     wv::SbdIdsParams ip{};
     sbd_fill(ix, ip);
-    ip.ids = hp.cand;
+    ip.ids = cand;
     ip.n_rows = N;
     ip.chunk_len = 1024;
     ip.n_chunks = (int)std::min<int64_t>(((int64_t)ccap + 1023) / 1024, 65535);
     ip.nq = nq;
-    ip.cand_cnt = hp.ccnt;
+    ip.cand_cnt = bp.ccnt;
     ip.n_elig = ix->sbd_nelig.as<unsigned int>();
     ip.cand_cap = ccap;
     ip.key_cap = sp.cap;
@@ -729,6 +763,13 @@ int wv_index_set_sbd_key_pass(wv_index* ix, int on) {
     if (!ix) return fail(WV_EINVAL, "wv_index_set_sbd_key_pass: null index");
     std::lock_guard<std::mutex> g(ix->mu);
     ix->sbd_key_pass = on != 0;
+    return WV_OK;
+}
+
+int wv_index_set_sbd_wide_key_pass(wv_index* ix, int on) {
+    if (!ix) return fail(WV_EINVAL, "wv_index_set_sbd_wide_key_pass: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->sbd_wide_key_pass = on != 0;
     return WV_OK;
 }
 

@@ -156,6 +156,7 @@ struct wv_index {
     // wv_index_set_sbd_key_pass): bounds, candidate lists and counts, the
     // bitmaps' eligible-row counts, the overflowed queries; the last call's stats
     bool sbd_key_pass = false;
+    bool sbd_wide_key_pass = false;   // the same for D > 128 (wv_sbd_h16w.hip, wv_index_set_sbd_wide_key_pass)
     DevBuf sbd_bound, sbd_cand, sbd_ccnt, sbd_nelig, sbd_qidx;
     uint64_t sbd_kp_q = 0, sbd_kp_cand = 0, sbd_kp_over = 0;
     void* sbd_scr = nullptr;

@@ -472,6 +472,27 @@ struct SbdH16BoundParams {
     unsigned int* ccnt;       // [nq]
 };
 
+// The same filter for 128 < D <= 1024 (wv_sbd_h16w.hip): both operands stream
+// through LDS in 32-k chunks; 256-row tiles (HW_BN) of the h16w_index image,
+// query blocks of qblock queries.  bound and ccnt come from the prologue above.
+struct SbdH16WParams {
+    const void* X;            // corpus image (h16w_index), whole 256-row tiles
+    const void* Q;            // query image (h16_index), zero padded to whole query blocks
+    const float* xns;         // s |x|^2 per row (L2 only), whole tiles
+    const float* bound;       // [nq] key bound in scaled units (-inf: nothing passes)
+    const uint64_t* excl;     // tombstones, nil nodes, missing rows
+    const uint64_t* allow;    // nullable; [nq][allow_stride] or shared (stride 0)
+    uint64_t excl_nbits, allow_nbits, allow_stride, N;
+    int nq, metric;
+    int ns;                   // 16-k steps of both images: a multiple of HW_KC
+    int qblock;               // queries per block: 64 or 256 (HW_BQ)
+    int n_qblocks, n_seg;     // grid: corpus segments x query blocks
+    uint32_t ntiles, tiles_per_seg;   // 256-row tiles of the corpus; per segment
+    uint32_t* cand;           // [nq][ccap] row ids
+    unsigned int* ccnt;       // [nq] candidates found (counts past ccap)
+    int ccap;
+};
+
 // Flat search over per-query id lists (wv_flat_ids.hip; flat_search.go:24-58):
 // sparse query s is batch row sel[s], its list ids[off[sel[s]] .. off[sel[s] + 1])
 struct FlatIdsParams {

@@ -54,8 +54,9 @@
 // return), is counted from the bitmaps alone (sbd_h16_count_kernel), once for
 // a shared or absent list.
 //
-// Follow-ups, out of scope here: D > 128 (the wide image layout), the Go
-// binding, and making the switch (wv_index_set_sbd_key_pass) the default.
+// D > 128 (the wide image layout) has a filter of its own: wv_sbd_h16w.hip.
+// Follow-ups, out of scope here: the Go binding, and making the switch
+// (wv_index_set_sbd_key_pass) the default.
 // Measured at 1M x 128 (profiles/sbd_h16/README.md): 3.3x / 1.5x the scan's
 // speed at 64 queries and 4.5x / 3.9x at 1024 with about 100 / 5,000 rows
 // within the target; a single query is 10 % faster with 100 rows within and

@@ -421,6 +421,13 @@ class GPUVectorIndex:
         the default) on an uncompressed index with D <= 128.  Same answers."""
         check(lib().wv_index_set_sbd_key_pass(self._h, int(on)))
 
+    def set_sbd_wide_key_pass(self, on: bool = True):
+        """The same switch for 128 < D <= 1024 (the wide f16 image): the f16
+        MFMA filter with both operands streamed through LDS + the exact stage
+        (on) or the scan (off, the default).  Same answers; no effect on an
+        index with D <= 128, which set_sbd_key_pass governs."""
+        check(lib().wv_index_set_sbd_wide_key_pass(self._h, int(on)))
+
     def last_sbd_key_pass_stats(self):
         """The last search_by_vector_distance_batch: queries the f16 filter
         served, the candidates it found, queries it handed back to the scan."""

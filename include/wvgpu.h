@@ -57,7 +57,19 @@ typedef enum {
 } wv_status;
 
 /* distancer.Provider.Type() (distancer/provider.go:14-24) */
-typedef enum { WV_L2_SQUARED = 0, WV_DOT = 1, WV_COSINE_DOT = 2 } wv_metric;
+/* WV_MANHATTAN (distancer/manhattan.go: the serial fp32 sum of |a[i] - b[i]|)
+ * and WV_HAMMING (distancer/hamming.go: the count of elements that compare
+ * unequal as floats; -0 == +0, a NaN differs from everything) are served by a
+ * plain index only, and only flat: every search of such an index is the exact
+ * one (WV_MODE_AUTO and WV_MODE_EXACT; WV_MODE_HNSW is WV_ESTATE), with
+ * distances bit-identical to the reference's and rows ordered by (dist, id).
+ * wv_search_by_vector_distance* work as for the other metrics.  Refused with
+ * WV_ESTATE: the graph (wv_index_upload_graph, _build_graph, _extend_graph)
+ * and the quantizer (wv_index_set_pq, _fit_pq, wv_index_set_compressed(ix, 1)).
+ * wv_search_batch_ids answers every query through its bitmap route.
+ * wv_mirror_create and wv_group_create reject these metrics with WV_EINVAL:
+ * mirror, group and the Go constants are follow-ups. */
+typedef enum { WV_L2_SQUARED = 0, WV_DOT = 1, WV_COSINE_DOT = 2, WV_MANHATTAN = 3, WV_HAMMING = 4 } wv_metric;
 
 typedef enum {
     WV_MODE_AUTO = 0,   /* SearchByVector dispatch: flat if allow && !forbidFlat && |allow| < cutoff */

@@ -17,7 +17,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "wvgpu.h")
 
 WV_OK, WV_EINVAL, WV_EOOM, WV_EDEVICE, WV_ESTATE, WV_EDELETED = range(6)
 MODE_AUTO, MODE_EXACT, MODE_HNSW = 0, 1, 2
-METRICS = {"l2-squared": 0, "dot": 1, "cosine-dot": 2}
+METRICS = {"l2-squared": 0, "dot": 1, "cosine-dot": 2, "manhattan": 3, "hamming": 4}
 
 
 class WvConfig(C.Structure):

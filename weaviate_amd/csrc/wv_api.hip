@@ -190,7 +190,7 @@ void wv_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
 const char* wv_version(void) { return "wvgpu 0.1 (gfx950)"; }
 
 int wv_index_create(int dim, int metric, const wv_config* cfg, uint64_t capacity, wv_index** out) {
-    if (!out || dim <= 0 || metric < 0 || metric > 2 || capacity == 0 || capacity >= (1ull << 31))
+    if (!out || dim <= 0 || metric < 0 || metric > WV_HAMMING || capacity == 0 || capacity >= (1ull << 31))
         return fail(WV_EINVAL, "wv_index_create: bad argument");
     auto* ix = new wv_index();
     ix->dim = dim;
@@ -226,7 +226,9 @@ int wv_index_create(int dim, int metric, const wv_config* cfg, uint64_t capacity
     // fp32 MFMA pass for every scan
     // f16 key pass (wv_bf_h16_kernel) for D <= 128 unless an ablation switch
     // asks for the bf16x3 (WV_BF_SPLIT=1) or the fp32 (WV_BF_FP32=1) pass
-    ix->use_h16 = dim <= 16 * wv::HW_NS_MAX && !std::getenv("WV_BF_FP32") && !std::getenv("WV_BF_SPLIT");
+    // (manhattan, hamming: no image of either kind -- wv_l1.hip reads the fp32 rows)
+    const bool l1 = metric_is_l1(metric);
+    ix->use_h16 = !l1 && dim <= 16 * wv::HW_NS_MAX && !std::getenv("WV_BF_FP32") && !std::getenv("WV_BF_SPLIT");
     if (ix->use_h16) {
         // D > 128: the wide-D kernel, whose chunks are HW_KC 16-k steps
         ix->h16_wide = dim > 16 * wv::H_NS_MAX;
@@ -242,7 +244,7 @@ int wv_index_create(int dim, int metric, const wv_config* cfg, uint64_t capacity
         (void)hipMemsetAsync(ix->xns.p, 0, cap_rows * 4, ix->stream);
         (void)hipMemsetAsync(ix->ex_bits.p, 0, 4, ix->stream);
     }
-    ix->use_split = !ix->use_h16 && ix->ldx % wv::BF_BK == 0 && ix->ldx <= 128 && !std::getenv("WV_BF_FP32");
+    ix->use_split = !l1 && !ix->use_h16 && ix->ldx % wv::BF_BK == 0 && ix->ldx <= 128 && !std::getenv("WV_BF_FP32");
     if (ix->use_split && ix->xsplit.ensure(vbytes) != hipSuccess) {
         wv_index_destroy(ix);
         return fail(WV_EOOM, "wv_index_create: device allocation failed");
@@ -273,7 +275,7 @@ int wv_index_destroy(wv_index* ix) {
                       &ix->delta, &ix->dmask, &ix->dl_ids, &ix->dl_d, &ix->dl_n, &ix->dq_tmp, &ix->b_tgt, &ix->b_ci,
                       &ix->b_cd, &ix->b_cn, &ix->b_cnt0, &ix->b_cntu, &ix->b_rk, &ix->b_rn, &ix->b_rk2, &ix->b_rn2,
                       &ix->b_uk, &ix->b_ul, &ix->b_uo, &ix->b_nr, &ix->b_tmp, &ix->stat_acc, &ix->fbd_list,
-                      &ix->fbd_nf, &ix->fbd_over, &ix->fbd_cd, &ix->fbd_ci, &ix->fbd_cn, &ix->fbd_scr})
+                      &ix->fbd_nf, &ix->fbd_over, &ix->fbd_cd, &ix->fbd_ci, &ix->fbd_cn, &ix->fbd_scr, &ix->l1_part})
         b->release();
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     ix->allow_keep.release();
@@ -322,6 +324,7 @@ int wv_index_update_config(wv_index* ix, const wv_config* cfg) {
 // in step.  s_x is fixed by the first write and only ever lowered (then the
 // whole image is rebuilt) so that no element overflows f16.
 static int rows_written(wv_index* ix, const uint64_t* d_ids, uint64_t n, uint64_t first_id) {
+    if (metric_is_l1(ix->metric)) return WV_OK;   // (no norms, no image)
     unsigned int mb = 0;
     HIP_TRY(hipMemcpyAsync(&mb, ix->maxnorm.p, 4, hipMemcpyDeviceToHost, ix->stream));
     HIP_TRY(hipStreamSynchronize(ix->stream));
@@ -395,8 +398,9 @@ static int upload_rows(wv_index* ix, const float* src, bool device_src, int ld, 
     HIP_TRY(launch_pad_rows(dsrc, ld, n, ix->dim, dst, ix->ldx, ix->stream));
     if (ix->metric == WV_COSINE_DOT)  // normalize on write (insert.go:56-60, vector_cache.go:110-112)
         HIP_TRY(wv_launch_normalize(dst, dst, n, ix->dim, ix->ldx, ix->stream));
-    HIP_TRY(wv_launch_rownorm(dst, n, ix->dim, ix->ldx, ix->xnorm.as<float>() + first_id,
-                              ix->maxnorm.as<unsigned int>(), ix->stream));
+    if (!metric_is_l1(ix->metric))   // (manhattan, hamming: no row norms)
+        HIP_TRY(wv_launch_rownorm(dst, n, ix->dim, ix->ldx, ix->xnorm.as<float>() + first_id,
+                                  ix->maxnorm.as<unsigned int>(), ix->stream));
     if (ix->use_split)
         HIP_TRY(wv_launch_split_rows(dst, ix->ldx, nullptr, n, n, ix->dim, 1.f, ix->xsplit.p, ix->ldx, first_id,
                                      ix->stream));
@@ -492,7 +496,8 @@ int wv_index_add(wv_index* ix, const uint64_t* ids_in, const float* rows_in, uin
     HIP_TRY(hipMemcpyAsync(d_ids, ids, n * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_pad_rows(ix->stage.as<float>(), ix->dim, n, ix->dim, tmp, ix->ldx, s));
     if (ix->metric == WV_COSINE_DOT) HIP_TRY(wv_launch_normalize(tmp, tmp, n, ix->dim, ix->ldx, s));
-    HIP_TRY(wv_launch_rownorm(tmp, n, ix->dim, ix->ldx, nrm, ix->maxnorm.as<unsigned int>(), s));
+    if (metric_is_l1(ix->metric)) HIP_TRY(hipMemsetAsync(nrm, 0, n * 4, s));   // (no row norms)
+    else HIP_TRY(wv_launch_rownorm(tmp, n, ix->dim, ix->ldx, nrm, ix->maxnorm.as<unsigned int>(), s));
     hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)n), dim3(128), 0, s, tmp, ix->ldx, d_ids, n, ix->ldx,
                        ix->vecs.as<float>(), nrm, ix->xnorm.as<float>());
     HIP_TRY(hipGetLastError());
@@ -628,6 +633,7 @@ int wv_index_set_pq(wv_index* ix, int segments, int centroids, int use_bits_enco
     if (check(ix) || !centroid_table || segments <= 0 || ix->dim % segments || !L.init(centroids, use_bits_encoding) ||
         (encoder != WV_PQ_TILE && encoder != WV_PQ_KMEANS))
         return fail(WV_EINVAL, "wv_index_set_pq: bad argument (segments must divide dims, 2 <= centroids <= 65536)");
+    if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_set_pq");
     std::lock_guard<std::mutex> g(ix->mu);
     HIP_TRY(hipSetDevice(ix->cfg.device));
     ix->pq_m = segments;
@@ -667,6 +673,7 @@ constexpr uint64_t FIT_GROUP_BYTES = 1ull << 30;
 int wv_index_fit_pq(wv_index* ix, int segments, int centroids, int use_bits_encoding, const float* init_table,
                     uint64_t seed, float* out_table, int32_t* out_iterations, uint64_t* out_reseeded) {
     if (!ix) return fail(WV_EINVAL, "wv_index_fit_pq: null index");
+    if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_fit_pq");
     if (segments <= 0) segments = ix->dim;   // compress.go:54-56
     CodeLayout L;
     if (ix->dim % segments || !L.init(centroids, use_bits_encoding != 0))
@@ -853,6 +860,7 @@ int wv_index_set_compressed(wv_index* ix, int on) {
     if (check(ix)) return WV_EINVAL;
     std::lock_guard<std::mutex> g(ix->mu);
     if (on) {
+        if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_set_compressed");
         if (!ix->pq_set) return fail(WV_ESTATE, "wv_index_set_compressed: no quantizer (wv_index_set_pq)");
         for (uint64_t w = 0; w < ix->bm_words; ++w)
             if (ix->has_vec[w] & ~ix->has_code[w])

@@ -1104,6 +1104,41 @@ __device__ void scan_rows(const ScanParams& p, const float* qv) {
     }
 }
 
+// Manhattan and hamming: the reference's serial fp32 chain in dimension order
+// (wv_l1.hip), one thread per row, the row walked in float4s (its padding and
+// qv's are zero: they add +0).  Neighbouring lanes read ldx floats apart, so
+// no load is coalesced: this is the fallback for k > L1_KMAX and for a
+// distance search that outgrew its list (once per query and deepening round,
+// k = 100, 1100, ...), not a path to batch on.
+template <int METRIC>
+__device__ void scan_rows_serial(const ScanParams& p, const float* qv) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.N; r += stride) {
+        const float* x = p.X + r * p.ldx;
+        float sum = 0.f;
+        for (int i = 0; i < p.D; i += 4) {
+            const float4 xv = *reinterpret_cast<const float4*>(x + i);
+            const float4 q = make_float4(qv[i], qv[i + 1], qv[i + 2], qv[i + 3]);
+            if (METRIC == WV_METRIC_MANHATTAN) {
+                sum += fabsf(q.x - xv.x);
+                sum += fabsf(q.y - xv.y);
+                sum += fabsf(q.z - xv.z);
+                sum += fabsf(q.w - xv.w);
+            } else {
+                sum += q.x != xv.x ? 1.f : 0.f;
+                sum += q.y != xv.y ? 1.f : 0.f;
+                sum += q.z != xv.z ? 1.f : 0.f;
+                sum += q.w != xv.w ? 1.f : 0.f;
+            }
+        }
+        bool ok = true;
+        if (p.tomb) ok = !bit_test(p.tomb, p.tomb_nbits, r);
+        if (p.allow && ok) ok = bit_test(p.allow, p.allow_nbits, r);
+        p.dist[r] = ok ? sum : __builtin_inff();
+        p.ids[r] = (uint32_t)r;
+    }
+}
+
 __global__ __launch_bounds__(256) void wv_exact_scan_kernel(ScanParams p) {
     extern __shared__ float qv[];
     // the tail reads whole float4s: zero-fill up to the padded length
@@ -1111,7 +1146,9 @@ __global__ __launch_bounds__(256) void wv_exact_scan_kernel(ScanParams p) {
     __syncthreads();
     if (p.metric == WV_METRIC_L2) scan_rows<WV_METRIC_L2>(p, qv);
     else if (p.metric == WV_METRIC_DOT) scan_rows<WV_METRIC_DOT>(p, qv);
-    else scan_rows<WV_METRIC_COSINE>(p, qv);
+    else if (p.metric == WV_METRIC_COSINE) scan_rows<WV_METRIC_COSINE>(p, qv);
+    else if (p.metric == WV_METRIC_MANHATTAN) scan_rows_serial<WV_METRIC_MANHATTAN>(p, qv);
+    else if (p.metric == WV_METRIC_HAMMING) scan_rows_serial<WV_METRIC_HAMMING>(p, qv);
 }
 
 // ---------------------------------------------------------------------------
@@ -1608,7 +1645,10 @@ hipError_t wv_launch_exact_scan(const wv::ScanParams* p, hipStream_t s) {
     uint64_t blocks = (p->N + 31) / 32;
     if (blocks > 8192) blocks = 8192;
     if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(wv::wv_exact_scan_kernel, dim3((unsigned)blocks), dim3(256), p->D * sizeof(float), s, *p);
+    if (p->metric < WV_METRIC_L2 || p->metric > WV_METRIC_HAMMING) return hipErrorInvalidValue;
+    // (the query row zero-filled to whole float4s)
+    hipLaunchKernelGGL(wv::wv_exact_scan_kernel, dim3((unsigned)blocks), dim3(256), ((p->D + 3) & ~3) * sizeof(float), s,
+                       *p);
     return hipGetLastError();
 }
 

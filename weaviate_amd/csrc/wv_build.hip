@@ -193,6 +193,7 @@ static int insert_batches(wv_index* ix, int ef_construction, int batch_div, uint
 int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int batch_div) {
     if (check(ix) || ef_construction < 1 || ef_construction > wv::HNSW_EF_MAX || batch_div < 1)
         return fail(WV_EINVAL, "wv_index_build_graph: bad argument");
+    if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_build_graph");
     std::lock_guard<std::mutex> guard(ix->mu);
     HIP_TRY(hipSetDevice(ix->cfg.device));
     hipStream_t s = ix->stream;
@@ -276,6 +277,7 @@ int wv_index_extend_graph(wv_index* ix, int ef_construction, uint64_t seed, int 
         return fail(WV_EINVAL, "wv_index_extend_graph: ef_construction outside 1.." + std::to_string(wv::HNSW_EF_MAX));
     if (batch_div < 1) return fail(WV_EINVAL, "wv_index_extend_graph: batch_div < 1");
     if (check(ix)) return WV_EINVAL;
+    if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_extend_graph");
     std::lock_guard<std::mutex> guard(ix->mu);
     if (!ix->has_graph || ix->gn == 0) return fail(WV_ESTATE, "wv_index_extend_graph: the index has no graph");
     const uint64_t gn = ix->gn, n = ix->n_rows;
@@ -428,6 +430,7 @@ int wv_index_upload_graph(wv_index* ix, uint64_t n, const int8_t* levels, const 
                           const uint32_t* upper_row, const uint32_t* upper, uint64_t n_upper, int degU, int max_level,
                           uint64_t entrypoint) {
     if (check(ix)) return WV_EINVAL;
+    if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_upload_graph");
     if (n == 0 || n > ix->capacity || !levels || !layer0 || deg0 <= 0 || deg0 > 256 || max_level < 0 ||
         entrypoint >= n || (max_level > 0 && (!upper_row || !upper || degU <= 0 || degU > 256)))
         return fail(WV_EINVAL, "wv_index_upload_graph: bad argument");

@@ -15,7 +15,7 @@
 #define WV_FLAG 0x80000000u   // "expanded" flag carried in bit 31 of a local id
 #define WV_IDMASK 0x7FFFFFFFu
 
-enum { WV_METRIC_L2 = 0, WV_METRIC_DOT = 1, WV_METRIC_COSINE = 2 };
+enum { WV_METRIC_L2 = 0, WV_METRIC_DOT = 1, WV_METRIC_COSINE = 2, WV_METRIC_MANHATTAN = 3, WV_METRIC_HAMMING = 4 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 

@@ -423,6 +423,22 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                     }
                     pp.s = sp;
                     HIP_TRY(wv_launch_sbd_pq_scan(&pp, s));
+                } else if (metric_is_l1(ix->metric)) {
+                    // manhattan, hamming: the tiled kernel's threshold epilogue (wv_l1.hip)
+                    wv::L1Params lp{};
+                    l1_fill(ix, &lp);
+                    lp.Q = sp.Q;
+                    lp.ldq = sp.dpad;
+                    lp.nq = nq;
+                    lp.allow = sp.allow;
+                    lp.allow_nbits = sp.allow_nbits;
+                    lp.allow_stride = sp.allow_stride;
+                    l1_schedule_for(ix, nq, &lp);
+                    lp.target = sp.target;
+                    lp.cap = cap;
+                    lp.keys = sp.keys;
+                    lp.cnt = sp.cnt;
+                    HIP_TRY(wv_launch_l1_thresh(&lp, s));
                 } else if (sbd_h16_ok(ix)) {
                     ccap = sbd_h16_cand(cap);
                     scan_p = sp;
@@ -589,7 +605,7 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
         hipStream_t s = ix->stream;
         N = ix->n_rows;
         ix->sbd_ids_list_q = ix->sbd_ids_list_ids = ix->sbd_ids_hnsw_q = ix->sbd_ids_legacy_q = 0;
-        if (ix->pq_on ? !sbd_pq_enabled() : ix->dpad > wv::FLAT_IDS_DPAD_MAX) {
+        if (ix->pq_on ? !sbd_pq_enabled() : ix->dpad > wv::FLAT_IDS_DPAD_MAX || metric_is_l1(ix->metric)) {
             // the uncompressed kernel keeps the query row in LDS (the
             // compressed ones read it from memory): the per-query path
             for (int q = 0; q < nq; ++q) legacy.push_back(q);

@@ -295,6 +295,7 @@ extern "C" {
 
 hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s) {
     if (p->ns == 0) return hipSuccess;
+    if (p->metric > WV_METRIC_COSINE) return hipErrorInvalidValue;   // (no branch for it: never the cosine one)
     if (p->k < 1 || p->k > 256 || p->n_chunks < 1 || p->n_chunks > 65535 || p->dpad > wv::FLAT_IDS_DPAD_MAX ||
         p->chunk_len == 0 || (p->n_chunks > 1 && !p->part))
         return hipErrorInvalidValue;
@@ -315,6 +316,7 @@ hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s) {
 
 hipError_t wv_launch_flat_ids_pq(const wv::FlatIdsPqParams* p, hipStream_t s) {
     if (p->ns == 0) return hipSuccess;
+    if (p->metric > WV_METRIC_COSINE) return hipErrorInvalidValue;   // (no branch for it: never the cosine one)
     if (p->k < 1 || p->k > 256 || p->n_chunks < 1 || p->n_chunks > 65535 || p->chunk_len == 0 ||
         p->chunk_len % 256 || (p->n_chunks > 1 && !p->part) || !wv::pq_ok(p->pq))
         return hipErrorInvalidValue;

@@ -395,6 +395,11 @@ int wv_group_create(const int* devices, int n_devices, int dim, int metric, cons
     if (!devices || n_devices < 1 || dim < 1 || !cfg || !out || capacity == 0 ||
         (layout != WV_GROUP_SHARD && layout != WV_GROUP_REPLICA))
         return gfail(WV_EINVAL, "wv_group_create: bad argument");
+    // (manhattan and hamming are single-index metrics so far: wv_index_create would take them)
+    if (metric < WV_L2_SQUARED || metric > WV_COSINE_DOT)
+        return gfail(WV_EINVAL, metric == WV_MANHATTAN || metric == WV_HAMMING
+                                    ? "wv_group_create: the manhattan and hamming metrics are served by a plain index only"
+                                    : "wv_group_create: unknown metric");
     // the device merge (wv_merge_shards_device) takes at most 16 shard lists
     if (layout == WV_GROUP_SHARD && n_devices > 16)
         return gfail(WV_EINVAL, "wv_group_create: at most 16 shard members");

@@ -237,9 +237,22 @@ struct wv_index {
     uint64_t fi_sparse_q = 0, fi_sparse_ids = 0, fi_bitmap_q = 0;   // the last call's routes
     hipEvent_t fi_ev[2] = {nullptr, nullptr};                       // the sparse kernel (timing on)
     bool fi_timed = false;
+    DevBuf l1_part;   // manhattan / hamming k-NN (wv_l1.hip): the segments' sorted keys
 };
 
 namespace wv_host {
+
+// manhattan and hamming: fp32 rows only (no normalisation, images, norms,
+// graph or quantizer), searched by wv_l1.hip
+inline bool metric_is_l1(int metric) { return metric == WV_MANHATTAN || metric == WV_HAMMING; }
+inline const char* metric_name(int metric) {
+    static const char* const names[] = {"l2-squared", "dot", "cosine-dot", "manhattan", "hamming"};
+    return metric >= 0 && metric <= 4 ? names[metric] : "?";
+}
+// the refusal of what such an index does not serve; fn: the entry point
+inline int refuse_l1(const wv_index* ix, const char* fn) {
+    return fail(WV_ESTATE, std::string(fn) + ": not served for the " + metric_name(ix->metric) + " metric");
+}
 
 // one pinned staging slot of wv_search_batch, returned when the call ends
 struct SlotLease {

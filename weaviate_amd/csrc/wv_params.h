@@ -408,6 +408,40 @@ struct SbdParams {
     const int* qidx;          // nullable: grid column i scans query qidx[i] of the batch, nq of them (null: query i)
 };
 
+// Manhattan and hamming distances (wv_l1.hip): one tiled VALU kernel, a
+// BQ-query x L1_BN-row tile per 256-thread workgroup, with a k-NN epilogue
+// (per-query LDS pools, then l1_merge_kernel over the segments) or the
+// threshold epilogue of SearchByVectorDistance.
+constexpr int L1_BN = 128;          // corpus rows per tile
+constexpr int L1_BK = 16;           // k-chunk staged through LDS
+constexpr int L1_BQ_WIDE = 64;      // queries per block, 4 x 8 accumulators per thread
+constexpr int L1_BQ_NARROW = 8;     // the same for small batches, 1 x 4 per thread
+constexpr int L1_NARROW_NQ = 128;   // batches of up to this many queries take the narrow block (profiles/l1/README.md)
+constexpr int L1_KMAX = 128;        // k the pools serve: L1_KMAX + L1_BN keys fit one 256-key sort
+struct L1Params {
+    const float* X;           // [N][ldx]
+    const float* Q;           // [nq][ldq]; columns past D are not read as data
+    const uint64_t* excl;     // tombstones, nil nodes, missing rows
+    const uint64_t* allow;    // nullable; [nq][allow_stride] or shared
+    uint64_t excl_nbits, allow_nbits, allow_stride, N;
+    int D, ldx, ldq, metric, nq;
+    int narrow;               // L1_BQ_NARROW-query blocks
+    uint32_t ntiles, tiles_per_seg;   // L1_BN-row tiles; a workgroup's run of them
+    int n_seg;                // segments: grid.x
+    // k-NN
+    int k;
+    unsigned long long* part; // [nq][n_seg][k] sorted fin_keys, L1_EMPTY padded
+    uint64_t id_base;
+    uint64_t* out_ids;        // [nq][k]
+    float* out_d;             // [nq][k]
+    int32_t* out_n;           // [nq]
+    // threshold (SbdParams' meaning)
+    const float* target;      // [nq]
+    int cap;
+    unsigned long long* keys; // [nq][cap]
+    unsigned int* cnt;        // [nq][3]
+};
+
 // The threshold pass over per-query allow lists given as ids (wv_sbd.hip,
 // sbd_ids_kernel): the queries [q0, q0 + nq) of a batch, each with a segment
 // of seg_cap[i] = min(list length, cap) keys that starts at seg_beg[i]

@@ -191,6 +191,7 @@ extern "C" {
 
 hipError_t wv_launch_sbd_ids(const wv::SbdIdsParams* p, hipStream_t s) {
     if (p->nq == 0 || p->n_chunks == 0) return hipSuccess;
+    if (p->metric > WV_METRIC_COSINE) return hipErrorInvalidValue;   // (no branch for it: never the cosine one)
     if (p->dpad > wv::FLAT_IDS_DPAD_MAX || p->n_chunks < 0 || p->n_chunks > 65535 || p->chunk_len == 0 ||
         p->chunk_len % 256)
         return hipErrorInvalidValue;
@@ -236,6 +237,7 @@ hipError_t wv_sbd_ids_sort(unsigned long long* keys, unsigned long long* tmp, in
 hipError_t wv_launch_sbd_scan(const wv::SbdParams* p, hipStream_t s) {
     if (p->nq == 0 || p->N == 0) return hipSuccess;
     if (p->dpad > 1024) return hipErrorInvalidValue;
+    if (p->metric > WV_METRIC_COSINE) return hipErrorInvalidValue;   // (no branch for it: never the cosine one)
     const uint64_t blocks_y = (p->N + p->rows_per_block - 1) / p->rows_per_block;
     if (blocks_y > 65535) return hipErrorInvalidValue;
     const dim3 grid((unsigned)p->nq, (unsigned)blocks_y);

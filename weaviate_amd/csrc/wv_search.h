@@ -67,6 +67,9 @@ struct PinLayout {
 // wv_search_exact.hip: flatSearch -- the key passes, their fallback, the PQ scan
 int run_exact(wv_index* ix, const Batch& b, const uint64_t* d_rowmask = nullptr, uint64_t rowmask_nbits = 0);
 int queue_fbd(wv_index* ix, const Batch& b);
+// the manhattan / hamming kernel's view of the index, and its schedule for nq queries (lp->N set)
+void l1_fill(const wv_index* ix, wv::L1Params* lp);
+void l1_schedule_for(const wv_index* ix, int nq, wv::L1Params* lp);
 // each query (pick null) or each query with pick[q] != 0 by a full scan and
 // sort of its own; counted in ix->last_fallbacks
 int exact_each(wv_index* ix, const Batch& b, const int32_t* pick);

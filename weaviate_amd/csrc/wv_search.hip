@@ -82,6 +82,11 @@ int count_allow_rows(wv_index* ix, const Batch& b, uint64_t words, std::vector<u
 
 // Core: device queries already padded to dpad and normalized (cosine).
 int search_core(wv_index* ix, const Batch& b, int ef, int mode) {
+    // a manhattan or hamming index has no graph: AUTO and EXACT are the flat search
+    if (metric_is_l1(ix->metric)) {
+        if (mode == WV_MODE_HNSW) return refuse_l1(ix, "WV_MODE_HNSW");
+        mode = WV_MODE_EXACT;
+    }
     int rc = refresh_bitmaps(ix);
     if (rc) return rc;
     hipStream_t s = b.s;
@@ -424,7 +429,8 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
         const bool can_hnsw = ix->has_graph && ef_eff <= wv::HNSW_EF_MAX;
         // (compressed: the list kernel over the codes, where the index asks
         // for it -- its query row stays in memory, so any dimension)
-        const bool sparse_ok = k <= wv::BF_WIDE_KMAX &&
+        // (manhattan, hamming: no list kernel, every query by its bitmap row)
+        const bool sparse_ok = k <= wv::BF_WIDE_KMAX && !metric_is_l1(ix->metric) &&
                                (ix->pq_on ? ix->pq_list_search : ix->dpad <= wv::FLAT_IDS_DPAD_MAX);
         std::vector<int32_t> sel[3];   // sparse, bitmap rows searched flat, bitmap rows searched by HNSW
         uint64_t sp_ids = 0, sp_max = 0;

@@ -570,9 +570,81 @@ int run_h16(wv_index* ix, const Batch& b, uint64_t N, const uint32_t* rowidx = n
     return queue_fbd(ix, b);
 }
 
+// The schedule both epilogues of wv_l1.hip share.  The block width comes from
+// the batch.  Segments are runs of whole tiles, and their number per query
+// block is chosen so that the grid fills whole rounds of the CUs' workgroup
+// slots (one wide workgroup per CU; three narrow ones: LDS admits four, the
+// manhattan block's 159 VGPRs three): from slots / blocks upwards, the first
+// count whose last round is at least 90 % full, else the fullest tried.
+// 157 wide blocks (10,000 queries) on 256 CUs take 3 segments each, 92 %,
+// where one segment each left 39 % of the CUs idle.
+// WV_L1_SEGS caps the segments per query block and WV_L1_NARROW_NQ moves the
+// switch-over; both are read per call (tests, measurements).
+// An empty index (N = 0) gets one empty segment: the launchers return early.
+void l1_schedule(const wv_index* ix, int nq, uint64_t N, wv::L1Params* lp) {
+    lp->narrow = nq <= env_int("WV_L1_NARROW_NQ", wv::L1_NARROW_NQ, 0) ? 1 : 0;
+    const int bq = lp->narrow ? wv::L1_BQ_NARROW : wv::L1_BQ_WIDE;
+    const uint64_t nqb = (uint64_t)std::max(1, (nq + bq - 1) / bq);
+    const uint64_t ntiles = (N + wv::L1_BN - 1) / wv::L1_BN;
+    const uint64_t slots = (uint64_t)std::max(1, ix->n_cus) * (lp->narrow ? 3 : 1);
+    const uint64_t lo = std::max<uint64_t>(1, slots / nqb);
+    uint64_t n_seg = lo;
+    double fullest = 0.0;
+    for (uint64_t n = lo; n <= 4 * lo + 4; ++n) {
+        const uint64_t wgs = n * nqb, rounds = (wgs + slots - 1) / slots;
+        const double full = (double)wgs / (double)(rounds * slots);
+        if (full > fullest + 1e-9) { fullest = full; n_seg = n; }
+        if (full >= 0.9) break;
+    }
+    n_seg = std::min(std::min(n_seg, (uint64_t)env_int("WV_L1_SEGS", INT_MAX, 1)), std::max<uint64_t>(ntiles, 1));
+    lp->ntiles = (uint32_t)ntiles;
+    lp->tiles_per_seg = (uint32_t)std::max<uint64_t>(1, (ntiles + n_seg - 1) / n_seg);
+    lp->n_seg = (int)std::max<uint64_t>(1, (ntiles + lp->tiles_per_seg - 1) / lp->tiles_per_seg);
+}
+
+// flatSearch of a manhattan or hamming index, k <= L1_KMAX: the tiled kernel
+// over every row (its epilogue applies tombstones and either kind of allow
+// list), then the merge of the segments.  Exact as computed: no fallback.
+int run_l1(wv_index* ix, const Batch& b) {
+    hipStream_t s = b.s;
+    wv::L1Params lp{};
+    l1_fill(ix, &lp);
+    lp.Q = b.q;
+    lp.ldq = b.ldq;
+    lp.nq = b.nq;
+    lp.allow = b.allow;
+    lp.allow_nbits = b.allow_nbits;
+    lp.allow_stride = b.allow_stride;
+    l1_schedule(ix, b.nq, lp.N, &lp);
+    lp.k = b.k;
+    HIP_TRY(ix->l1_part.ensure((size_t)b.nq * lp.n_seg * b.k * 8));
+    lp.part = ix->l1_part.as<unsigned long long>();
+    lp.id_base = ix->cfg.id_base;
+    lp.out_ids = b.out_ids;
+    lp.out_d = b.out_d;
+    lp.out_n = b.out_n;
+    TREC(0);
+    HIP_TRY(wv_launch_l1_knn(&lp, s));
+    TREC(1);
+    return WV_OK;
+}
+
 }  // namespace
 
 namespace wv_host {
+
+// what wv_l1.hip reads of the index
+void l1_fill(const wv_index* ix, wv::L1Params* lp) {
+    lp->X = ix->vecs.as<float>();
+    lp->excl = ix->excl.as<uint64_t>();
+    lp->excl_nbits = ix->capacity;
+    lp->N = ix->n_rows;
+    lp->D = ix->dim;
+    lp->ldx = ix->ldx;
+    lp->metric = ix->metric;
+}
+
+void l1_schedule_for(const wv_index* ix, int nq, wv::L1Params* lp) { l1_schedule(ix, nq, lp->N, lp); }
 
 // Queue the device-resolved fallback for the queries whose flag in ix->fail
 // is set (threshold ix->fail_thr): no host round trip (wv_bf.hip, fbd kernels).
@@ -637,6 +709,8 @@ int run_exact(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_t 
     const uint64_t allow_nbits = b.allow_nbits, allow_stride = b.allow_stride;
     hipStream_t s = b.s;
     if (N == 0 || nq == 0) return no_rows(b);
+    // manhattan, hamming: one kernel whatever the filter; larger k by scan and sort
+    if (metric_is_l1(ix->metric)) return k <= wv::L1_KMAX ? run_l1(ix, b) : exact_each(ix, b, nullptr);
     // the f16 pass (whole corpus or a shared allow list) serves k up to
     // BF_WIDE_KMAX; the other key passes k up to BF_FAST_KMAX
     const bool h16_ok = ix->use_h16 && !allow_stride && !d_rowmask;

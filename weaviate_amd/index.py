@@ -77,7 +77,7 @@ class GPUVectorIndex:
                  dynamic_ef_factor: int = 8, flat_search_cutoff: int = 40000, forbid_flat: bool = False,
                  id_base: int = 0):
         if distance not in METRICS:
-            raise WvError(1, f"unsupported distance {distance!r} (l2-squared, dot, cosine-dot)")
+            raise WvError(1, f"unsupported distance {distance!r} ({', '.join(METRICS)})")
         self.dim, self.distance, self.capacity = dim, distance, capacity
         self.cfg = WvConfig()
         lib().wv_config_default(C.byref(self.cfg))
@@ -580,8 +580,8 @@ class GPUGroup:
     def __init__(self, devices, dim: int, distance: str = "l2-squared", capacity: int = 1 << 20, *,
                  layout: str = "shard", max_connections: int = 64, ef: int = -1, flat_search_cutoff: int = 40000,
                  forbid_flat: bool = False):
-        if distance not in METRICS:
-            raise WvError(1, f"unsupported distance {distance!r}")
+        if distance not in ("l2-squared", "dot", "cosine-dot"):   # (manhattan, hamming: a plain index only)
+            raise WvError(1, f"distance {distance!r} is not served by a group (l2-squared, dot, cosine-dot)")
         self.dim, self.distance, self.capacity, self.layout = dim, distance, capacity, layout
         self.cfg = WvConfig()
         lib().wv_config_default(C.byref(self.cfg))

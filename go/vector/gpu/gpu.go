@@ -156,6 +156,20 @@ func lastErr(op string, rc C.int) error {
 	return errors.Errorf("wvgpu %s: status %d: %s", op, int(rc), C.GoString(C.wv_last_error()))
 }
 
+// SetPQScan is wv_index_set_pq_scan for an embedder that holds a wv_index
+// handle of its own: flat k-NN on a compressed index by the fused scan.  The
+// mirror behind Index keeps the library default (off).
+func SetPQScan(ix unsafe.Pointer, on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.wv_index_set_pq_scan((*C.wv_index)(ix), v); rc != 0 {
+		return lastErr("set_pq_scan", rc)
+	}
+	return nil
+}
+
 func configOf(uc ent.UserConfig, device int) C.wv_config {
 	var cfg C.wv_config
 	C.wv_config_default(&cfg)

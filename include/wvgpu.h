@@ -403,6 +403,24 @@ int wv_search_batch_ids(wv_index *ix, const float *queries, int nq, int k, int e
  * (Off by default because the suite pins the bitmap route's counts for a
  * compressed index; making on the library default is a follow-up.) */
 int wv_index_set_pq_list_search(wv_index *ix, int on);
+/* Flat k-NN on a compressed index -- mode EXACT, allow lists below the flat
+ * cutoff, per-query bitmaps, the delta rows of a mutable index -- by the fused
+ * scan (on): one kernel computes the PQ distances of a slab of rows for up to
+ * four queries at once from lookup tables in LDS and selects each query's k
+ * rows as it goes, for k <= 256.  Off (the default), and for larger k, every
+ * (query, row) distance is written out and a segmented sort orders them.  The
+ * answers are the same bits either way: (dist, id) order, -0 tied with +0.
+ * The setting may be made before or after compression and has no effect on an
+ * uncompressed index; a null index returns WV_EINVAL.
+ * WV_PQ_SCAN_GROUP=1|2|4 and WV_PQ_SCAN_ROWS=<rows>, read per call, ask for
+ * the queries per workgroup and the rows per workgroup (rounded up to 256);
+ * a group whose tables do not fit falls back to the library's choice.  For
+ * tests and A/B runs. */
+int wv_index_set_pq_scan(wv_index *ix, int on);
+/* The last search on the index (nullable outputs): the queries its flat search
+ * over PQ codes answered by the fused scan and by the sort route.  Both are 0
+ * after a search that ran no such flat search. */
+int wv_last_pq_scan_stats(wv_index *ix, uint64_t *fused_queries, uint64_t *sorted_queries);
 /* The last wv_search_batch_ids on the index (nullable outputs): queries answered
  * by the sparse flat kernel, ids handed to it, queries sent down the bitmap route. */
 int wv_last_sparse_stats(wv_index *ix, uint64_t *sparse_queries, uint64_t *sparse_ids, uint64_t *bitmap_queries);

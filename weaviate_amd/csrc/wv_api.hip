@@ -878,6 +878,21 @@ int wv_index_set_pq_list_search(wv_index* ix, int on) {
     return WV_OK;
 }
 
+int wv_index_set_pq_scan(wv_index* ix, int on) {
+    if (!ix) return fail(WV_EINVAL, "wv_index_set_pq_scan: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->pq_scan = on != 0;
+    return WV_OK;
+}
+
+int wv_last_pq_scan_stats(wv_index* ix, uint64_t* fused_queries, uint64_t* sorted_queries) {
+    if (!ix) return fail(WV_EINVAL, "wv_last_pq_scan_stats: null index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (fused_queries) *fused_queries = ix->pq_fused_q;
+    if (sorted_queries) *sorted_queries = ix->pq_sorted_q;
+    return WV_OK;
+}
+
 int wv_search_time_ef(const wv_index* ix, int k) { return ix ? search_time_ef(ix->cfg, k) : -1; }
 int wv_config_search_time_ef(const wv_config* cfg, int k) { return cfg ? search_time_ef(*cfg, k) : -1; }
 

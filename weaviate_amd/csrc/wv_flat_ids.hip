@@ -20,106 +20,13 @@
 // row per lane, from the query's lookup table in LDS (wv_pq_lut.h) or from
 // pq_dist_row -- the same bits.
 #include "wv_device.h"
+#include "wv_fi_select.h"
 #include "wv_launch.h"
 #include "wv_params.h"
 #include "wv_pq_lut.h"
 #include "wv_topk.h"
 
 namespace wv {
-
-constexpr uint64_t FI_EMPTY = ~0ull;
-constexpr int FI_STAGE = 256;   // staged keys per wave
-constexpr int FI_STEP = 64;     // ids per wave step
-
-__device__ __forceinline__ void fi_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint64_t fi_shfl(uint64_t v, int src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64);
-    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// The last phase of bitonic256_wave: a bitonic run of 256 keys, ascending after.
-__device__ __forceinline__ void bitonic_merge256_wave(uint64_t (&kk)[4], int lane) {
-    auto cas = [&](auto jc, auto pc) {   // (literal register indices, as in bitonic256_wave)
-        constexpr int j = decltype(jc)::value, pj = decltype(pc)::value;
-        const bool sw = kk[pj] < kk[j];
-        const uint64_t t = kk[j];
-        kk[j] = sw ? kk[pj] : kk[j];
-        kk[pj] = sw ? t : kk[pj];
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    cas(I0{}, I2{}); cas(I1{}, I3{});
-    cas(I0{}, I1{}); cas(I2{}, I3{});
-#pragma unroll
-    for (int jj = 32; jj > 0; jj >>= 1) {
-        const bool lower = (lane & jj) == 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t plo = (uint32_t)__shfl_xor((int)(uint32_t)kk[j], jj, 64);
-            const uint32_t phi = (uint32_t)__shfl_xor((int)(uint32_t)(kk[j] >> 32), jj, 64);
-            const uint64_t pk = ((uint64_t)phi << 32) | plo;
-            // the lower lane keeps the min
-            const uint64_t a = lower ? pk : kk[j], b = lower ? kk[j] : pk;
-            kk[j] = a < b ? pk : kk[j];
-        }
-    }
-}
-
-// top (ascending) <- the 256 smallest of top and desc (descending)
-__device__ __forceinline__ void fi_merge(uint64_t (&top)[4], const uint64_t (&desc)[4], int lane) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) top[j] = desc[j] < top[j] ? desc[j] : top[j];
-    bitonic_merge256_wave(top, lane);
-}
-
-// the wave's cnt staged keys into top
-__device__ __forceinline__ void fi_flush(uint64_t (&top)[4], const uint64_t* stage, int cnt, int lane) {
-    uint64_t st[4];
-    // sorted ascending as complements = descending as keys (an empty slot's complement is 0)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) st[j] = 64 * j + lane < cnt ? ~stage[64 * j + lane] : 0ull;
-    bitonic256_wave(st, lane);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) st[j] = ~st[j];
-    fi_merge(top, st, lane);
-}
-
-// element k - 1 of top, in every lane
-__device__ __forceinline__ uint64_t fi_kth(const uint64_t (&top)[4], int k) {
-    const int j = (k - 1) >> 6;
-    const uint64_t v = j == 0 ? top[0] : j == 1 ? top[1] : j == 2 ? top[2] : top[3];
-    return fi_shfl(v, (k - 1) & 63);
-}
-
-// (P: FlatIdsParams or FlatIdsPqParams -- the same output fields)
-template <int METRIC, class P>
-__device__ __forceinline__ void fi_write(const P& p, const uint64_t (&top)[4], int q, int lane) {
-    int n = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = 64 * j + lane;
-        const bool has = i < p.k && top[j] != FI_EMPTY;
-        if (has) {
-            float d;
-            uint32_t id;
-            fin_unkey(top[j], d, id);
-            // fin_key folds -0 into +0; a dot product of exactly 0 is the
-            // distance -0 (the sums themselves are never -0)
-            if (METRIC == WV_METRIC_DOT && d == 0.f) d = -0.0f;
-            p.out_ids[(size_t)q * p.k + i] = p.id_base + id;
-            p.out_d[(size_t)q * p.k + i] = d;
-        }
-        n += __popcll(__ballot(has));
-    }
-    if (lane == 0) p.out_n[q] = n;
-}
 
 // The end of a workgroup's walk: each wave's last staged keys flushed, the
 // waves merged through their stages, and wave 0 writes the query's output rows
@@ -259,6 +166,7 @@ __global__ __launch_bounds__(256) void flat_ids_pq_kernel(FlatIdsPqParams p) {
 }
 
 // one wave per query: its chunks' sorted keys merged, then the output rows
+// (sel null: query s is batch row s)
 template <int METRIC>
 __global__ __launch_bounds__(64) void flat_ids_merge_kernel(FlatIdsParams p) {
     const int s = blockIdx.x, lane = threadIdx.x;
@@ -273,7 +181,7 @@ __global__ __launch_bounds__(64) void flat_ids_merge_kernel(FlatIdsParams p) {
         }
         fi_merge(top, od, lane);
     }
-    fi_write<METRIC>(p, top, p.sel[s], lane);
+    fi_write<METRIC>(p, top, p.sel ? p.sel[s] : s, lane);
 }
 
 // bitmap rows of the queries sel[0 .. nsel) from their id lists (rows zeroed
@@ -293,6 +201,21 @@ __global__ __launch_bounds__(256) void ids_to_bits_kernel(const uint32_t* ids, c
 
 extern "C" {
 
+// The chunks' sorted keys (part, [ns][n_chunks][k]) merged per query into the
+// output rows: what the list kernels and the PQ scan (wv_pq_scan.hip) end
+// with.  Reads sel (nullable), id_base, part, ns, n_chunks, metric, k and the
+// outputs of *p.
+hipError_t wv_launch_flat_ids_merge(const wv::FlatIdsParams* p, hipStream_t s) {
+    if (p->ns == 0) return hipSuccess;
+    if (p->k < 1 || p->k > 256 || p->n_chunks < 1 || !p->part) return hipErrorInvalidValue;
+    // (the metric only decides how a zero distance is written)
+    if (p->metric == WV_METRIC_DOT)
+        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_DOT>, dim3(p->ns), dim3(64), 0, s, *p);
+    else
+        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_L2>, dim3(p->ns), dim3(64), 0, s, *p);
+    return hipGetLastError();
+}
+
 hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s) {
     if (p->ns == 0) return hipSuccess;
     if (p->metric > WV_METRIC_COSINE) return hipErrorInvalidValue;   // (no branch for it: never the cosine one)
@@ -306,12 +229,7 @@ hipError_t wv_launch_flat_ids(const wv::FlatIdsParams* p, hipStream_t s) {
     else hipLaunchKernelGGL(wv::flat_ids_kernel<WV_METRIC_COSINE>, grid, dim3(256), lds, s, *p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p->n_chunks == 1) return e;
-    // (the metric only decides how a zero distance is written)
-    if (p->metric == WV_METRIC_DOT)
-        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_DOT>, dim3(p->ns), dim3(64), 0, s, *p);
-    else
-        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_L2>, dim3(p->ns), dim3(64), 0, s, *p);
-    return hipGetLastError();
+    return wv_launch_flat_ids_merge(p, s);
 }
 
 hipError_t wv_launch_flat_ids_pq(const wv::FlatIdsPqParams* p, hipStream_t s) {
@@ -341,11 +259,7 @@ hipError_t wv_launch_flat_ids_pq(const wv::FlatIdsPqParams* p, hipStream_t s) {
     mp.out_ids = pp.out_ids;
     mp.out_d = pp.out_d;
     mp.out_n = pp.out_n;
-    if (mp.metric == WV_METRIC_DOT)
-        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_DOT>, dim3(mp.ns), dim3(64), 0, s, mp);
-    else
-        hipLaunchKernelGGL(wv::flat_ids_merge_kernel<WV_METRIC_L2>, dim3(mp.ns), dim3(64), 0, s, mp);
-    return hipGetLastError();
+    return wv_launch_flat_ids_merge(&mp, s);
 }
 
 hipError_t wv_launch_ids_to_bits(const uint32_t* ids, const uint64_t* off, const int32_t* sel, int nsel,

@@ -180,10 +180,13 @@ struct wv_index {
     int pq_m = 0, pq_ks = 0, pq_ds = 0, pq_encoder = 0;
     bool pq_set = false, pq_on = false, pq_use_bits = false;
     bool pq_list_search = false;   // wv_index_set_pq_list_search: flat queries of wv_search_batch_ids walk their lists
+    bool pq_scan = false;          // wv_index_set_pq_scan: flat k-NN by the fused scan (wv_pq_scan.hip), k <= 256
     uint64_t pq_stride = 0;
     std::vector<uint64_t> has_code;
     DevBuf pq_cent, pq_codes;
     DevBuf pk_key, pk_dist, pk_val, pk_skey, pk_sval, pk_off;
+    DevBuf pk_part;                // the fused scan's sorted keys per (query, slab)
+    uint64_t pq_fused_q = 0, pq_sorted_q = 0;   // the last search's flat queries by route (wv_last_pq_scan_stats)
     // stats of the last batch: host-side counts plus device accumulators
     // (stat_acc: distance evaluations, expansions, device-resolved
     // fallbacks), read -- after a sync -- only when the stats are asked for

@@ -592,6 +592,52 @@ struct PqScanParams {
     uint32_t* val;           // [nqc][nr] j
 };
 
+// The same search with the selection fused into the scan (wv_pq_scan.hip):
+// grid (query groups, row slabs); a workgroup serves `group` queries over its
+// slab from tables interleaved by query (lut[(i * ks + c) * group + g]), or,
+// group == 0, one query by pq_dist_row.  Slabs merge through `part`.
+struct PqKnnParams {
+    PqParams pq;
+    const float* Q;          // [nq][ldq] prepared queries (normalized for cosine)
+    const uint32_t* rows;    // [nr] ascending row ids (nullable: rows 0..nr-1)
+    const uint64_t* excl;    // excluded rows (tombstones, nil nodes, rows without a code)
+    const uint64_t* allow;   // one row of allow_stride words per query (nullable)
+    uint64_t excl_nbits, allow_nbits, allow_stride;
+    uint64_t nr;
+    uint64_t slab_rows;      // rows per slab: a multiple of 256
+    uint64_t id_base;
+    unsigned long long* part;   // [nq][n_slabs][k] sorted keys (n_slabs > 1)
+    int nq, ldq, metric, k;
+    int n_slabs;
+    int group;               // 4, 2, 1: queries per workgroup, from tables; 0: one, evaluated directly
+    uint64_t* out_ids;       // [nq][k]
+    float* out_d;
+    int32_t* out_n;
+};
+constexpr int PQ_KNN_STAGE = 128;            // staged keys per (wave, query): flushed past 64
+constexpr int PQ_KNN_LDS = 80 << 10;         // the launcher's own choice: two workgroups in a CU's 160 KiB
+constexpr int PQ_KNN_LDS_MAX = 160 << 10;    // what a requested group may take
+// LDS of a workgroup serving g queries (0: direct): their tables and stages,
+// and at least the slab merge's 4 x 256 keys per query
+inline size_t pq_knn_lds(const PqParams& pq, int g) {
+    const size_t q = g ? (size_t)g : 1;
+    const size_t walk = 4 * q * PQ_KNN_STAGE * 8 + (size_t)g * pq.m * pq.ks * 4;
+    const size_t merge = 4 * q * 256 * 8;
+    return walk > merge ? walk : merge;
+}
+// Queries per workgroup: `want` (4, 2 or 1) where its tables fit the CU, else
+// two, or one, within PQ_KNN_LDS; 0 where a query's table is past
+// SBD_PQ_LUT_BYTES_MAX (the other PQ kernels' limit).  Four is never the
+// launcher's own choice: measured at 1M x 128, 32 x 256 it lost to two at
+// every batch size (1.00 against 0.75 ms at 64 queries, 10.1 against 9.0 at
+// 1,024); two against one is 0.34 / 0.28 ms at 8 queries, 0.75 / 1.08 at 64,
+// 9.0 / 8.2 at 1,024 (profiles/pq_scan/README.md).
+inline int pq_knn_group(const PqParams& pq, int want) {
+    if ((uint64_t)pq.m * (uint64_t)pq.ks * 4 > (uint64_t)(64 << 10)) return 0;
+    if ((want == 4 || want == 2 || want == 1) && pq_knn_lds(pq, want) <= (size_t)PQ_KNN_LDS_MAX) return want;
+    return pq_knn_lds(pq, 2) <= (size_t)PQ_KNN_LDS ? 2 : 1;
+}
+
 // The two threshold passes on a compressed index (wv_sbd_pq.hip): the same
 // outputs from the PQ distance (pq_dist_row's bits).  A workgroup whose share
 // of rows is at least lut_min_rows builds the query's lookup table
@@ -601,6 +647,7 @@ struct PqScanParams {
 // (SBD_PQ_LUT_BYTES_MAX) and the share is at least ks rows, 0 = never, 1 =
 // wherever it fits.  X, D and ldx of the wrapped blocks are not read.
 constexpr int SBD_PQ_LUT_BYTES_MAX = 64 << 10;   // two 256-thread workgroups share a CU's 160 KiB
+static_assert(SBD_PQ_LUT_BYTES_MAX == 64 << 10, "pq_knn_group states the same limit");
 struct SbdPqParams {
     SbdParams s;
     PqParams pq;

@@ -1,8 +1,10 @@
 // wv_search_exact.hip -- flatSearch on the device: the key passes of wv_bf.hip
 // and wv_h16.hip with allow-list compaction and the device-resolved fallback,
-// the scan over PQ codes (wv_pq.hip), and the per-query full scan and sort.
+// the scan over PQ codes (wv_pq.hip; fused with the selection: wv_pq_scan.hip),
+// and the per-query full scan and sort.
 #include <hipcub/hipcub.hpp>
 
+#include "wv_pq_lut.h"
 #include "wv_search.h"
 
 using namespace wv_host;
@@ -190,8 +192,60 @@ __global__ void iota_stride_kernel(int32_t* off, int n, int64_t stride) {
     if (i <= n) off[i] = (int32_t)(i * stride);
 }
 
+// The fused scan (wv_pq_scan.hip) over the nr rows of `rows` (nullable: rows
+// 0..nr-1): the queries per workgroup and the rows per slab.
+// The group is two queries where their tables and stages leave room for a
+// second workgroup in the CU, else one (pq_knn_group; WV_PQ_SCAN_GROUP=1|2|4
+// asks for another, honoured where it fits the CU at all).  Slabs are whole
+// wave rounds (256 rows), enough of them for two workgroups per CU over the
+// grid, but at least 16 ks rows each where a table is built.  A slab costs a
+// table build (what ks direct rows cost), the first fills of every wave's
+// selection and a step of the one-wave merge of a query's slabs; the list
+// kernel's floor of 4 ks left one query over 1M rows at 0.64 ms (489 slabs)
+// where slabs of 4,096 rows take 0.38 and of 16,384 rows 0.29, while 100,000
+// compacted rows are fastest at 4,096 (0.22 against 0.26 at 1,024 and 0.32 at
+// 16,384): profiles/pq_scan/README.md.
+// WV_PQ_SCAN_ROWS=<rows> sets the slab instead.  Both are read per call.
+int run_pq_knn(wv_index* ix, const Batch& b, const uint32_t* rows, uint64_t nr) {
+    wv::PqKnnParams kp{};
+    kp.pq = pq_params(ix);
+    kp.group = wv::pq_knn_group(kp.pq, env_int("WV_PQ_SCAN_GROUP", 0));
+    const uint64_t per = kp.group ? kp.group : 1, n_groups = ((uint64_t)b.nq + per - 1) / per;
+    const uint64_t want = std::max<uint64_t>(1, (2 * (uint64_t)ix->n_cus + n_groups - 1) / n_groups);
+    auto whole = [](uint64_t r) { return std::max<uint64_t>(256, (r + 255) / 256 * 256); };
+    uint64_t slab = std::max(whole((nr + want - 1) / want), kp.group ? whole(16 * (uint64_t)kp.pq.ks) : 256);
+    if (const int r = env_int("WV_PQ_SCAN_ROWS", 0, 1)) slab = whole((uint64_t)r);
+    slab = std::max(slab, whole((nr + 65534) / 65535));   // (the grid's y limit)
+    kp.slab_rows = slab;
+    kp.n_slabs = (int)((nr + slab - 1) / slab);
+    if (kp.n_slabs > 1) {
+        HIP_TRY(ix->pk_part.ensure((size_t)b.nq * kp.n_slabs * b.k * 8));
+        kp.part = ix->pk_part.as<unsigned long long>();
+    }
+    kp.Q = b.q;
+    kp.rows = rows;
+    kp.excl = ix->excl.as<uint64_t>();
+    kp.excl_nbits = ix->capacity;
+    kp.allow = b.allow_stride ? b.allow : nullptr;   // a shared list is compacted already
+    kp.allow_nbits = b.allow_nbits;
+    kp.allow_stride = b.allow_stride;
+    kp.nr = nr;
+    kp.id_base = ix->cfg.id_base;
+    kp.nq = b.nq;
+    kp.ldq = b.ldq;
+    kp.metric = ix->metric;
+    kp.k = b.k;
+    kp.out_ids = b.out_ids;
+    kp.out_d = b.out_d;
+    kp.out_n = b.out_n;
+    HIP_TRY(wv_launch_pq_knn(&kp, b.s));
+    return WV_OK;
+}
+
 // flatSearch over PQ codes: the rows a shared allow list (or the delta mask)
-// keeps are compacted, every (query, row) distance is computed from the codes
+// keeps are compacted; then, where the index asks for it (wv_index_set_pq_scan)
+// and k <= 256, the fused scan selects each query's rows as it computes their
+// distances.  Otherwise every (query, row) distance is computed from the codes
 // and a stable segmented radix sort orders each query's row list by
 // (dist, id); queries go in chunks of at most 2^26 (query, row) pairs.
 int run_pq_flat(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_t rowmask_nbits) {
@@ -199,6 +253,8 @@ int run_pq_flat(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_
     const int nq = b.nq;
     hipStream_t s = b.s;
     if (N == 0 || nq == 0) return no_rows(b);
+    const bool fused = ix->pq_scan && b.k <= 256 && wv::pq_ok(pq_params(ix));
+    (fused ? ix->pq_fused_q : ix->pq_sorted_q) += (uint64_t)nq;
     const bool shared = b.allow && !b.allow_stride;
     const uint64_t* cmask = shared ? b.allow : d_rowmask;
     const uint64_t cbits = shared ? b.allow_nbits : rowmask_nbits;
@@ -210,6 +266,7 @@ int run_pq_flat(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_
         if (nr == 0) return no_rows(b);
         rows = ix->rowidx.as<uint32_t>();
     }
+    if (fused) return run_pq_knn(ix, b, rows, nr);
     const uint64_t cap = 1ull << 26;
     const int qc = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)nq, cap / nr));
     const uint64_t items = (uint64_t)qc * nr;

@@ -305,6 +305,19 @@ class GPUVectorIndex:
         Same answers; no effect on an uncompressed index."""
         check(lib().wv_index_set_pq_list_search(self._h, int(on)))
 
+    def set_pq_scan(self, on: bool = True):
+        """Flat k-NN on a compressed index (k <= 256) by the fused scan (on) or
+        the scan-and-sort route (off, the default).  Same answers; no effect
+        on an uncompressed index."""
+        check(lib().wv_index_set_pq_scan(self._h, int(on)))
+
+    def last_pq_scan_stats(self):
+        """The last search: the queries its flat search over PQ codes answered
+        by the fused scan and by the sort route."""
+        a, b = C.c_uint64(), C.c_uint64()
+        check(lib().wv_last_pq_scan_stats(self._h, C.byref(a), C.byref(b)))
+        return {"fused_queries": a.value, "sorted_queries": b.value}
+
     def set_tombstones(self, ids: Iterable[int]):
         al = AllowList.from_ids(ids, self.capacity)
         check(lib().wv_index_set_tombstones(self._h, _ptr(al.words), al.nbits))

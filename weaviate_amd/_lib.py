@@ -115,6 +115,8 @@ SIGNATURES = {
     "wv_index_set_pq_list_search": (C.c_int, [_vp, C.c_int]),
     "wv_index_set_pq_scan": (C.c_int, [_vp, C.c_int]),
     "wv_last_pq_scan_stats": (C.c_int, [_vp, _u64p, _u64p]),
+    "wv_index_set_large_k": (C.c_int, [_vp, C.c_int]),
+    "wv_last_large_k_stats": (C.c_int, [_vp, _u64p, _u64p]),
     "wv_last_sparse_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "wv_last_sparse_time": (C.c_int, [_vp, _f32p]),
     "wv_index_query_ld": (C.c_int, [_vp]),

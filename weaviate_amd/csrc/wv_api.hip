@@ -280,7 +280,8 @@ int wv_index_destroy(wv_index* ix) {
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     ix->allow_keep.release();
     for (DevBuf* b : {&ix->sbd_t, &ix->sbd_keys, &ix->sbd_tmp, &ix->sbd_cnt, &ix->sbd_off, &ix->sbd_q, &ix->sbd_seg,
-                      &ix->sbd_bound, &ix->sbd_cand, &ix->sbd_ccnt, &ix->sbd_nelig, &ix->sbd_qidx})
+                      &ix->sbd_bound, &ix->sbd_cand, &ix->sbd_ccnt, &ix->sbd_nelig, &ix->sbd_qidx, &ix->bigk_seg,
+                      &ix->bigk_flag})
         b->release();
     if (ix->sbd_scr) (void)hipFree(ix->sbd_scr);
     ix->sbd_scr = nullptr;

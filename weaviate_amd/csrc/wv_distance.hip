@@ -30,8 +30,16 @@ bool sbd_pq_enabled() {
     return !(e && e[0] == '0' && !e[1]);
 }
 int sbd_pq_lut() { return env_tri("WV_SBD_PQ_LUT"); }
-// entries of a query's list (WV_SBD_CAP, read per call)
-int sbd_cap() { return env_int("WV_SBD_CAP", 16384, 128); }
+
+// A batch here keeps its lists and counts in the ix->sbd_* buffers while its
+// round 1 runs k-NN searches on the same stream: marked, so that the large-k
+// route, which borrows those buffers, leaves such a search to the per-query
+// route (ix->mu is held throughout)
+struct SbdBusy {
+    wv_index* ix;
+    explicit SbdBusy(wv_index* x) : ix(x) { ix->sbd_busy = true; }
+    ~SbdBusy() { ix->sbd_busy = false; }
+};
 
 // Round 1 (limit 100) of the queries that search by HNSW, on the host: slot[q]
 // is query q's row of ids / d ([nh][100]) and n ([nh]), -1 where round 1 is
@@ -66,6 +74,24 @@ void sbd_fill(const wv_index* ix, P& sp) {
     sp.metric = ix->metric;
     sp.keys = ix->sbd_keys.as<unsigned long long>();
     sp.cnt = ix->sbd_cnt.as<unsigned int>();
+}
+
+}  // namespace
+
+// shared with the large-k route (wv_search_bigk.hip): wv_search.h
+namespace wv_host {
+
+// entries of a query's list (WV_SBD_CAP, read per call)
+int sbd_cap() { return env_int("WV_SBD_CAP", wv::SBD_CAP, 128); }
+
+// rows per workgroup of the scan: ~4 blocks per CU over the scanned queries,
+// whole 4-wave steps of 256 rows
+uint64_t sbd_scan_rows(const wv_index* ix, uint64_t N, int nqs) {
+    const uint64_t target_blocks = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 4 / (uint64_t)nqs);
+    uint64_t rpb = std::max<uint64_t>(4096, (N + target_blocks - 1) / target_blocks);
+    rpb = (rpb + 255) / 256 * 256;
+    while ((N + rpb - 1) / rpb > 65535) rpb *= 2;
+    return rpb;
 }
 
 // The f16 threshold filter and its exact stage in place of the scan
@@ -214,6 +240,9 @@ int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s)
     return WV_OK;
 }
 
+}  // namespace wv_host
+
+namespace {
 // the search.go:90-158 loop over an exact sorted list (from round r0: 1 when
 // round 1 is exact too, 2 after an HNSW round 1): the end of the kept prefix
 int64_t sbd_exact_rounds(int r0, int64_t Qn, int64_t A, int64_t n, int64_t max_limit) {
@@ -360,6 +389,7 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
         std::vector<std::vector<unsigned long long>> lists(nq);
         {
             std::lock_guard<std::mutex> g(ix->mu);
+            SbdBusy busy(ix);
             hipStream_t s = ix->stream;
             int rc = refresh_bitmaps(ix);
             if (rc) return rc;
@@ -376,14 +406,6 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
             bool passed = false, keyed = false;   // keyed: the f16 filter ran in place of the scan
             wv::SbdParams scan_p{};               // the scan's parameters, kept for the filter's overflow
             int ccap = 0;
-            // ~4 blocks per CU over the scanned queries, whole 4-wave steps of 256 rows
-            auto scan_rows = [&](uint64_t N, int nqs) {
-                const uint64_t target_blocks = std::max<uint64_t>(1, (uint64_t)ix->n_cus * 4 / (uint64_t)nqs);
-                uint64_t rpb = std::max<uint64_t>(4096, (N + target_blocks - 1) / target_blocks);
-                rpb = (rpb + 255) / 256 * 256;
-                while ((N + rpb - 1) / rpb > 65535) rpb *= 2;
-                return rpb;
-            };
             auto launch_pass = [&]() -> int {
                 int rc = stage_queries(ix, queries, nq, &dq, s);
                 if (rc) return rc;
@@ -403,7 +425,7 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 sp.allow_stride = allow_stride_words;
                 sp.N = ix->n_rows;
                 sp.nq = nq;
-                sp.rows_per_block = scan_rows(sp.N, nq);
+                sp.rows_per_block = sbd_scan_rows(ix, sp.N, nq);
                 sp.cap = cap;
                 if (ix->pq_on) {
                     wv::SbdPqParams pp{};
@@ -516,7 +538,7 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                     for (int q : over) HIP_TRY(hipMemsetAsync(ix->sbd_cnt.as<unsigned int>() + 3 * (size_t)q, 0, 12, s));
                     scan_p.qidx = ix->sbd_qidx.as<int>();
                     scan_p.nq = (int)over.size();
-                    scan_p.rows_per_block = scan_rows(scan_p.N, scan_p.nq);
+                    scan_p.rows_per_block = sbd_scan_rows(ix, scan_p.N, scan_p.nq);
                     HIP_TRY(wv_launch_sbd_scan(&scan_p, s));
                     HIP_TRY(wv_sbd_sort(ix->sbd_keys.as<unsigned long long>(), ix->sbd_tmp.as<unsigned long long>(),
                                         ix->sbd_cnt.as<unsigned int>(), nq, cap, ix->sbd_off.as<int>(), &ix->sbd_scr,
@@ -601,6 +623,7 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
         uint64_t* off = reinterpret_cast<uint64_t*>(pin + o_f);
         if (int rc = ids_stage(fn, allow_ids, allow_offsets, nq, ids32, off)) return rc;
         std::lock_guard<std::mutex> g(ix->mu);
+        SbdBusy busy(ix);
         HIP_TRY(hipSetDevice(ix->cfg.device));
         hipStream_t s = ix->stream;
         N = ix->n_rows;

@@ -159,6 +159,12 @@ struct wv_index {
     bool sbd_wide_key_pass = false;   // the same for D > 128 (wv_sbd_h16w.hip, wv_index_set_sbd_wide_key_pass)
     DevBuf sbd_bound, sbd_cand, sbd_ccnt, sbd_nelig, sbd_qidx;
     uint64_t sbd_kp_q = 0, sbd_kp_cand = 0, sbd_kp_over = 0;
+    // exact k-NN for large k (wv_bigk.hip, wv_index_set_large_k): the route
+    // borrows the buffers above (sbd_busy: a distance batch holds them); its
+    // segments' keys and flags, and the last search's queries by route
+    bool large_k = false, sbd_busy = false;
+    DevBuf bigk_seg, bigk_flag;
+    uint64_t bigk_batched_q = 0, bigk_legacy_q = 0;
     void* sbd_scr = nullptr;
     size_t sbd_scr_cap = 0;
     DevBuf scan_d, scan_i, sort_d, sort_i, sort_tmp;

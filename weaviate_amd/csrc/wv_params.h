@@ -393,6 +393,7 @@ struct HnswParams {
 
 // SearchByVectorDistance's threshold pass (wv_sbd.hip): per query, the
 // allowed rows within the target distance, with their sort keys and counts
+constexpr int SBD_CAP = 16384;   // entries of a query's list (WV_SBD_CAP overrides it per call)
 struct SbdParams {
     const float* X;
     const float* Q;           // [nq][dpad] (normalized if cosine)
@@ -525,6 +526,60 @@ struct SbdH16WParams {
     uint32_t* cand;           // [nq][ccap] row ids
     unsigned int* ccnt;       // [nq] candidates found (counts past ccap)
     int ccap;
+};
+
+// Exact k-NN for large k (wv_bigk.hip): a sampled bound tau per query turns
+// "the k nearest" into "every row within tau", which the threshold passes
+// above and the segmented sort answer for a whole chunk of queries at once.
+//
+// The bound pass ranks every step-th row of the corpus, step = max(1, k /
+// BIGK_SAMPLE), and takes the BIGK_RANK-th smallest distance of that sample.
+// A sample of one row in k / 16 holds on average 16 of the true k nearest, the
+// count being close to Poisson(16):
+//  * tau falls below the true k-th distance only if the sample holds
+//    BIGK_RANK or more of the k - 1 nearest: P(Poisson(16) >= 36) ~ 1e-5 per
+//    query;
+//  * the rows within tau number BIGK_RANK / BIGK_SAMPLE k = 2.25 k on average
+//    with relative sd 1 / sqrt(36) = 1/6, so a list of 4 k entries is the mean
+//    plus 4.7 sd: BIGK_KMAX = SBD_CAP / 4 (9.2 k +- 1.5 k rows against 16,384
+//    at k = 4096).
+// Neither event makes an answer wrong: the emit kernel counts, and a query
+// whose list overflowed or holds fewer than k rows within tau takes the
+// per-query scan and sort.
+constexpr int BIGK_SAMPLE = 16;            // sampled rows among the k nearest, on average
+constexpr int BIGK_RANK = 36;              // tau: this smallest distance of the sample
+constexpr int BIGK_KMAX = SBD_CAP / 4;     // 4096
+constexpr int BIGK_SEG_MIN = 1024;         // sampled rows per workgroup, at least (4 steps of 4 waves)
+// Small batches (profiles/large_k/README.md, 1M x 128): one long list is
+// sorted by one workgroup of the segmented sort, 0.14 ms at k = 1000 and 0.41
+// at 4096, so a single query beats its scan and sort (0.31 ms) only up to
+// k = 600, two or three queries up to k = 2000, and four or more at every k.
+constexpr int BIGK_ONE_QUERY_KMAX = 600;
+constexpr int BIGK_FEW_NQ = 3;
+constexpr int BIGK_FEW_QUERIES_KMAX = 2000;
+struct BigkParams {
+    const float* X;
+    const float* Q;           // [nq][dpad] (normalized if cosine)
+    const uint64_t* excl;     // tombstones, nil nodes, missing rows
+    const uint64_t* allow;    // nullable; [nq][allow_stride] or shared
+    uint64_t excl_nbits, allow_nbits, allow_stride, N;
+    int D, ldx, dpad, metric, nq, k;
+    // bound pass: sample j is row j step; a workgroup walks samples_per_seg of them
+    uint32_t step;
+    uint64_t n_samples, samples_per_seg;
+    int n_seg;
+    uint32_t* seg_keys;       // [nq][n_seg][64] ascending orderable distances, ~0 padded
+    float* tau;               // [nq] the threshold pass's targets
+    // emit: the sorted lists and counts of the threshold pass
+    const unsigned long long* sorted;   // [nq][cap]
+    const unsigned int* cnt;            // [nq][3]: |Q|, A (d <= tau), n
+    const unsigned int* ccnt;           // nullable: the f16 filter's candidate counts (past ccap: unanswered)
+    int cap, ccap;
+    uint64_t id_base;
+    uint64_t* out_ids;        // [nq][k]
+    float* out_d;             // [nq][k]
+    int32_t* out_n;           // [nq]
+    int32_t* flag;            // [nq] 1: the per-query route answers
 };
 
 // Flat search over per-query id lists (wv_flat_ids.hip; flat_search.go:24-58):

@@ -1,5 +1,6 @@
 // wv_search.h -- what the search host files share (wv_search.hip,
-// wv_search_exact.hip, wv_search_hnsw.hip, wv_distance.hip): the batch
+// wv_search_exact.hip, wv_search_bigk.hip, wv_search_hnsw.hip,
+// wv_distance.hip): the batch
 // descriptor every pipeline takes and the declarations that cross files.
 // Internal, like wv_index.h: hidden visibility.
 #pragma once
@@ -73,6 +74,22 @@ void l1_schedule_for(const wv_index* ix, int nq, wv::L1Params* lp);
 // each query (pick null) or each query with pick[q] != 0 by a full scan and
 // sort of its own; counted in ix->last_fallbacks
 int exact_each(wv_index* ix, const Batch& b, const int32_t* pick);
+
+// wv_search_bigk.hip: flatSearch for k past the key passes, a chunk of queries
+// at a time (bound pass, threshold pass, segmented sort, emit); whether
+// run_exact may hand it the batch
+bool bigk_ok(const wv_index* ix, const Batch& b);
+int run_bigk(wv_index* ix, const Batch& b);
+
+// wv_distance.hip: what the large-k route shares with the distance batches --
+// a list's entries, the scan's rows per workgroup, and the f16 threshold
+// filter with its exact stage (queries, targets, lists and counts in the
+// ix->sbd_* buffers; candidates and their counts in ix->sbd_cand / sbd_ccnt)
+int sbd_cap();
+uint64_t sbd_scan_rows(const wv_index* ix, uint64_t N, int nqs);
+bool sbd_h16_ok(const wv_index* ix);
+int sbd_h16_cand(int cap);
+int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s);
 
 // wv_search_hnsw.hip: the graph search, beside an exact pass over the delta set
 int choose_vc_log2(int per_wave_budget_words, int fixed_words, uint64_t n_nodes, int* tbits);

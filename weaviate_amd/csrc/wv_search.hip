@@ -93,6 +93,7 @@ int search_core(wv_index* ix, const Batch& b, int ef, int mode) {
     ix->last_dist = ix->last_exp = ix->last_fallbacks = 0;
     ix->last_side_rows = ix->last_side_xs = 0;
     ix->pq_fused_q = ix->pq_sorted_q = 0;
+    ix->bigk_batched_q = ix->bigk_legacy_q = 0;
     HIP_TRY(ix->stat_acc.ensure(48));
     HIP_TRY(hipMemsetAsync(ix->stat_acc.p, 0, 48, s));
     ix->stat_stream = s;

@@ -889,7 +889,9 @@ int run_exact(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_t 
         TREC(3);
         return queue_fbd(ix, b);
     }
-    // k past every key pass: each query by a full scan and sort
+    // k past every key pass: the batched large-k route where the index asks
+    // for it (wv_search_bigk.hip), else each query by a full scan and sort
+    if (bigk_ok(ix, b)) return run_bigk(ix, b);
     return exact_each(ix, b, nullptr);
 }
 

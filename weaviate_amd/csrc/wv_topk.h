@@ -334,4 +334,30 @@ __device__ __forceinline__ void bitonic256_wave(uint64_t (&kk)[4], int lane) {
     }
 }
 
+// A wave's sorted list of 64 u32 keys, one per lane (wv_bigk.hip): one
+// compare-exchange stage against lane ^ jj, the ascending bitonic sort (21
+// stages), the merge of a bitonic run (6), and the 64 smallest of two
+// ascending lists -- the element-wise minimum of an ascending and a reversed
+// ascending run is bitonic and holds them.
+__device__ __forceinline__ uint32_t wave_cas64(uint32_t v, int jj, bool keep_min) {
+    const uint32_t pv = (uint32_t)__shfl_xor((int)v, jj, 64);
+    return keep_min ? min(v, pv) : max(v, pv);
+}
+__device__ __forceinline__ uint32_t bitonic64_sort(uint32_t v, int lane) {
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1)
+#pragma unroll
+        for (int jj = k >> 1; jj > 0; jj >>= 1) v = wave_cas64(v, jj, ((lane & jj) == 0) == ((lane & k) == 0));
+    return v;
+}
+__device__ __forceinline__ uint32_t bitonic64_merge(uint32_t v, int lane) {
+#pragma unroll
+    for (int jj = 32; jj > 0; jj >>= 1) v = wave_cas64(v, jj, (lane & jj) == 0);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min64_of(uint32_t top, uint32_t asc, int lane) {
+    const uint32_t desc = (uint32_t)__shfl((int)asc, 63 - lane, 64);
+    return bitonic64_merge(min(top, desc), lane);
+}
+
 }  // namespace wv

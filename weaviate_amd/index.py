@@ -318,6 +318,19 @@ class GPUVectorIndex:
         check(lib().wv_last_pq_scan_stats(self._h, C.byref(a), C.byref(b)))
         return {"fused_queries": a.value, "sorted_queries": b.value}
 
+    def set_large_k(self, on: bool = True):
+        """Flat k-NN past every key pass (k > 256, or k > 32 with per-query
+        bitmaps; k <= 4096) by the batched large-k route (on) or a scan and
+        sort per query (off, the default).  Same answers."""
+        check(lib().wv_index_set_large_k(self._h, int(on)))
+
+    def last_large_k_stats(self):
+        """The last search: (queries the large-k route answered, queries it
+        handed to the per-query route)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        check(lib().wv_last_large_k_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def set_tombstones(self, ids: Iterable[int]):
         al = AllowList.from_ids(ids, self.capacity)
         check(lib().wv_index_set_tombstones(self._h, _ptr(al.words), al.nbits))

@@ -144,10 +144,55 @@ int wv_index_build_graph(wv_index *ix, int ef_construction, uint64_t seed, int b
  * 2 * cfg.max_connections / cfg.max_connections; a row in [graph n, n_rows)
  * without a vector; a nil or tombstoned node below graph n (insert.go keeps
  * deleted nodes out of its results, search.go:294, neighbor_connections.go:217,
- * and the build search has no tombstone set: rebuild instead).  Tombstones on
- * the new rows are no obstacle.  A device error after the checks leaves the
- * index without a graph. */
+ * and the build search has no tombstone set: clean up or rebuild instead).
+ * The nil nodes that wv_index_cleanup_tombstones made are no obstacle while
+ * the graph has no others (no list names one, so the build search never meets
+ * them).  Tombstones on the new rows are no obstacle.  A device error after
+ * the checks leaves the index without a graph. */
 int wv_index_extend_graph(wv_index *ix, int ef_construction, uint64_t seed, int batch_div, uint64_t *inserted);
+/* Remove the deleted nodes from the index's graph on the device
+ * (CleanUpTombstonedNodes, delete.go:177-224).  D is the set of tombstoned ids
+ * below graph n, taken once at entry; a live node is one with level >= 0 that
+ * is not in D.  The outputs are nullable.
+ *   flag      a live node is flagged if any of its lists, at any level up to
+ *             its own, names an id in D (connectionsPointTo, :378-388); the
+ *             flagged ids are processed in ascending order;
+ *   reassign  in batches of max(1, min(16384, live / batch_div)): every member
+ *             searches the graph as it stood before its batch, edges into D
+ *             included -- the ef = 1 descent from the entrypoint to its own
+ *             level, then ef_construction per level, D as deny list and the
+ *             member itself traversed but never a result
+ *             (neighbor_connections.go:212) -- and its lists are replaced by
+ *             selectNeighborsHeuristic's choice, M per level and 2M on layer
+ *             0; reverse links as in the build, except that a neighbour which
+ *             holds the member already keeps its list.  Members of one batch
+ *             do not see each other's new lists; a node keeps its level.
+ *             *reassigned = members re-linked;
+ *   strike    a member whose search overflowed its side set is not re-linked:
+ *             D's ids are struck from its lists, which close up in stored
+ *             order.  *struck = such members.  No node leaves the call with
+ *             an edge into D;
+ *   entrypoint  if it is in D: the lowest live id on the highest level that
+ *             holds a live node (findNewGlobalEntrypoint's outcome, :422-478),
+ *             max_level drops with it; `upper` keeps its level stride on the
+ *             device and wv_index_download_graph still delivers max_level
+ *             levels per row.  With no live node left the index has no graph
+ *             afterwards (resetIfEmpty) and D keeps its tombstones, which
+ *             alone keep its rows out of the flat search then;
+ *   remove    every id in D becomes a nil node (level -1, lists padded) and
+ *             loses its tombstone; as a nil node it stays out of every search.
+ *             *removed = |D|.  Tombstones at or above graph n are untouched.
+ * The same index and arguments give the same graph bits on every run.  With
+ * nothing in D: WV_OK, zero counts, nothing written.  WV_ESTATE before any
+ * write: no graph; degrees other than 2 * cfg.max_connections /
+ * cfg.max_connections; a compressed index; a manhattan or hamming index.
+ * WV_EINVAL: ef_construction outside [1, 512] or batch_div < 1.  A device
+ * error after the checks leaves the index without a graph.  The rows of the
+ * removed nodes stay uploaded: wv_index_build_graph would insert them again,
+ * so a caller that deletes extends (wv_index_extend_graph) rather than
+ * rebuilds.  Must not race with searches (as wv_index_reserve). */
+int wv_index_cleanup_tombstones(wv_index *ix, int ef_construction, int batch_div, uint64_t *reassigned,
+                                uint64_t *removed, uint64_t *struck);
 /* The index's graph in the wv_index_upload_graph layout (nullable outputs). */
 int wv_index_graph_info(wv_index *ix, uint64_t *n, int *deg0, int *degU, int *max_level, uint64_t *n_upper,
                         uint64_t *entrypoint);
@@ -702,6 +747,8 @@ typedef struct {
     wv_flush_fn flush;         /* nullable: called before a resync reads the log */
     void *flush_ctx;
     int resync_backoff_ms;     /* first delay before a resync (0: 1000) */
+    int cleanup_on_compact;    /* 1: without a commit log, a compaction removes the deleted nodes
+                                  (wv_index_cleanup_tombstones) and extends before it would rebuild */
 } wv_mirror_options;
 /* VectorForIDThunk for one doc id: WV_OK with *len = the vector's length
  * (copied to out when *len <= cap), WV_ENOTFOUND for a deleted object, any

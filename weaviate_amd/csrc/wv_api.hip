@@ -275,7 +275,8 @@ int wv_index_destroy(wv_index* ix) {
                       &ix->delta, &ix->dmask, &ix->dl_ids, &ix->dl_d, &ix->dl_n, &ix->dq_tmp, &ix->b_tgt, &ix->b_ci,
                       &ix->b_cd, &ix->b_cn, &ix->b_cnt0, &ix->b_cntu, &ix->b_rk, &ix->b_rn, &ix->b_rk2, &ix->b_rn2,
                       &ix->b_uk, &ix->b_ul, &ix->b_uo, &ix->b_nr, &ix->b_tmp, &ix->stat_acc, &ix->fbd_list,
-                      &ix->fbd_nf, &ix->fbd_over, &ix->fbd_cd, &ix->fbd_ci, &ix->fbd_cn, &ix->fbd_scr, &ix->l1_part})
+                      &ix->fbd_nf, &ix->fbd_over, &ix->fbd_cd, &ix->fbd_ci, &ix->fbd_cn, &ix->fbd_scr, &ix->l1_part,
+                      &ix->c_bits, &ix->c_wave, &ix->c_flag, &ix->c_st, &ix->c_ep})
         b->release();
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     ix->allow_keep.release();

@@ -1,7 +1,9 @@
 // wv_build.hip -- the index's HNSW graph: built on the device from the
 // uploaded rows (wv_index_build_graph), extended in place with the rows added
-// since (wv_index_extend_graph), uploaded from or downloaded to the host.
-// Kernels: wv_hnsw.hip ("GPU graph construction"), wv_graph_grow.hip.
+// since (wv_index_extend_graph), rid of its deleted nodes
+// (wv_index_cleanup_tombstones), uploaded from or downloaded to the host.
+// Kernels: wv_hnsw.hip ("GPU graph construction"), wv_graph_grow.hip,
+// wv_graph_cleanup.hip.
 #include <hipcub/hipcub.hpp>
 
 #include <chrono>
@@ -30,6 +32,40 @@ static int draw_level(uint64_t seed, uint64_t id, double normalizer) {
     const double u = ((double)(r >> 11) + 0.5) * (1.0 / 9007199254740992.0);
     const int t = (int)std::floor(-std::log(u) * normalizer);
     return t > 126 ? 126 : t;
+}
+
+// The reverse links of one batch (b.req_key / b.req_node, nreq of them, ~0 =
+// none): grouped by (level, neighbour) with the batch order kept (a stable
+// sort), one run per neighbour, then connectNeighborAtLevel per run
+// (wv_build_link_kernel).  sorted (nullable): recorded once the runs are known.
+static int link_requests(wv_index* ix, wv::BuildParams& b, size_t nreq, hipEvent_t sorted) {
+    hipStream_t s = ix->stream;
+    size_t tb = 0, tb2 = 0, tb3 = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ix->b_rk.as<uint64_t>(), ix->b_rk2.as<uint64_t>(),
+                                               ix->b_rn.as<uint32_t>(), ix->b_rn2.as<uint32_t>(), (int)nreq, 0, 64, s));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, tb2, ix->b_rk2.as<uint64_t>(), ix->b_uk.as<uint64_t>(),
+                                                  ix->b_ul.as<uint32_t>(), ix->b_nr.as<uint32_t>(), (int)nreq, s));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, ix->b_ul.as<uint32_t>(), ix->b_uo.as<uint32_t>(), (int)nreq,
+                                             s));
+    HIP_TRY(ix->b_tmp.ensure(std::max(tb, std::max(tb2, tb3))));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ix->b_tmp.p, tb, ix->b_rk.as<uint64_t>(), ix->b_rk2.as<uint64_t>(),
+                                               ix->b_rn.as<uint32_t>(), ix->b_rn2.as<uint32_t>(), (int)nreq, 0, 64, s));
+    HIP_TRY(hipMemsetAsync(ix->b_ul.p, 0, nreq * 4, s));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(ix->b_tmp.p, tb2, ix->b_rk2.as<uint64_t>(), ix->b_uk.as<uint64_t>(),
+                                                  ix->b_ul.as<uint32_t>(), ix->b_nr.as<uint32_t>(), (int)nreq, s));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ix->b_tmp.p, tb3, ix->b_ul.as<uint32_t>(), ix->b_uo.as<uint32_t>(),
+                                             (int)nreq, s));
+    uint32_t n_runs = 0;
+    if (sorted) HIP_TRY(hipEventRecord(sorted, s));
+    HIP_TRY(hipMemcpyAsync(&n_runs, ix->b_nr.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    b.run_key = ix->b_uk.as<uint64_t>();
+    b.run_off = ix->b_uo.as<uint32_t>();
+    b.run_len = ix->b_ul.as<uint32_t>();
+    b.sorted_node = ix->b_rn2.as<uint32_t>();
+    b.n_runs = (int)n_runs;
+    HIP_TRY(wv_launch_build_link(&b, s));
+    return WV_OK;
 }
 
 // insert.go:103-217 in batches (wv_hnsw.hip, "GPU graph construction"): the
@@ -125,35 +161,8 @@ static int insert_batches(wv_index* ix, int ef_construction, int batch_div, uint
         if (trace) HIP_TRY(hipEventRecord(tev[1], s));
         HIP_TRY(wv_launch_build_select(&b, s));
         if (trace) HIP_TRY(hipEventRecord(tev[2], s));
-        // reverse links grouped by (level, neighbour), batch order kept (stable)
-        size_t tb = 0, tb2 = 0, tb3 = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ix->b_rk.as<uint64_t>(), ix->b_rk2.as<uint64_t>(),
-                                                   ix->b_rn.as<uint32_t>(), ix->b_rn2.as<uint32_t>(), (int)nreq, 0, 64,
-                                                   s));
-        HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, tb2, ix->b_rk2.as<uint64_t>(), ix->b_uk.as<uint64_t>(),
-                                                      ix->b_ul.as<uint32_t>(), ix->b_nr.as<uint32_t>(), (int)nreq, s));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, ix->b_ul.as<uint32_t>(), ix->b_uo.as<uint32_t>(),
-                                                 (int)nreq, s));
-        HIP_TRY(ix->b_tmp.ensure(std::max(tb, std::max(tb2, tb3))));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ix->b_tmp.p, tb, ix->b_rk.as<uint64_t>(), ix->b_rk2.as<uint64_t>(),
-                                                   ix->b_rn.as<uint32_t>(), ix->b_rn2.as<uint32_t>(), (int)nreq, 0, 64,
-                                                   s));
-        HIP_TRY(hipMemsetAsync(ix->b_ul.p, 0, nreq * 4, s));
-        HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(ix->b_tmp.p, tb2, ix->b_rk2.as<uint64_t>(),
-                                                      ix->b_uk.as<uint64_t>(), ix->b_ul.as<uint32_t>(),
-                                                      ix->b_nr.as<uint32_t>(), (int)nreq, s));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ix->b_tmp.p, tb3, ix->b_ul.as<uint32_t>(), ix->b_uo.as<uint32_t>(),
-                                                 (int)nreq, s));
-        uint32_t n_runs = 0;
-        if (trace) HIP_TRY(hipEventRecord(tev[3], s));
-        HIP_TRY(hipMemcpyAsync(&n_runs, ix->b_nr.p, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        b.run_key = ix->b_uk.as<uint64_t>();
-        b.run_off = ix->b_uo.as<uint32_t>();
-        b.run_len = ix->b_ul.as<uint32_t>();
-        b.sorted_node = ix->b_rn2.as<uint32_t>();
-        b.n_runs = (int)n_runs;
-        HIP_TRY(wv_launch_build_link(&b, s));
+        if (int rc = link_requests(ix, b, nreq, trace ? tev[3] : nullptr)) return rc;
+        const uint32_t n_runs = (uint32_t)b.n_runs;
         if (trace) {
             HIP_TRY(hipEventRecord(tev[4], s));
             HIP_TRY(hipEventSynchronize(tev[4]));
@@ -241,8 +250,10 @@ int wv_index_build_graph(wv_index* ix, int ef_construction, uint64_t seed, int b
     ix->max_level = top;
     ix->n_upper = n_upper;
     ix->entrypoint = ep;
+    ix->upper_stride = ul;
     ix->has_graph = true;
     ix->any_nil = false;
+    ix->nil_cleaned = false;
     for (uint64_t i = 0; i < n; ++i) ix->pending_host[i >> 6] &= ~(1ull << (i & 63));
     ix->bitmaps_dirty = true;
     return WV_OK;
@@ -293,7 +304,7 @@ int wv_index_extend_graph(wv_index* ix, int ef_construction, uint64_t seed, int 
     // over a graph that holds nil or tombstoned nodes the caller rebuilds.
     for (uint64_t i = 0; i < gn; ++i) {
         const uint64_t bit = 1ull << (i & 63);
-        if (ix->nil_host[i >> 6] & bit)
+        if ((ix->nil_host[i >> 6] & bit) && !ix->nil_cleaned)   // (a cleanup's nil nodes: no list names one)
             return fail(WV_ESTATE, "wv_index_extend_graph: graph node " + std::to_string(i) + " is nil");
         if (ix->tomb_host[i >> 6] & bit)
             return fail(WV_ESTATE, "wv_index_extend_graph: graph node " + std::to_string(i) + " has a tombstone");
@@ -313,7 +324,7 @@ int wv_index_extend_graph(wv_index* ix, int ef_construction, uint64_t seed, int 
         maxL = std::max<int>(maxL, lv[i]);
         if (lv[i] >= 1) urow[i] = (uint32_t)n_upper++;
     }
-    const int ul_old = std::max(1, ix->max_level), ul = std::max(1, maxL);
+    const int ul_old = ix->upper_stride, ul = std::max(ul_old, maxL);
     const uint64_t nu_old = ix->n_upper;
     HIP_TRY(hipSetDevice(ix->cfg.device));
     hipStream_t s = ix->stream;
@@ -391,11 +402,290 @@ int wv_index_extend_graph(wv_index* ix, int ef_construction, uint64_t seed, int 
     }
     ix->gn = n;
     ix->max_level = top;
+    ix->upper_stride = ul;
     ix->n_upper = n_upper;
     ix->entrypoint = ep;
     ix->bitmaps_dirty = true;
     if (inserted) *inserted = k;
     return WV_OK;
+}
+
+// The device half of wv_index_cleanup_tombstones, the checks done: dead is D's
+// bitmap and skip is D plus the nil nodes (what a search may not return), both
+// over the graph's words; n_dead = |D|, n_live the other non-nil nodes.
+static int cleanup_device(wv_index* ix, int ef_construction, int batch_div, const std::vector<uint64_t>& dead,
+                          const std::vector<uint64_t>& skip, uint64_t n_live, uint64_t* reassigned, uint64_t* struck) {
+    hipStream_t s = ix->stream;
+    const uint64_t gn = ix->gn, words = dead.size();
+    const int M = ix->cfg.max_connections, M0 = 2 * M;
+    // the wave state of a tombstoned search (run_hnsw's first pass): a
+    // 256-entry side set, a 512-slot expanded set, 20 KiB per wave
+    // (WV_CLEANUP_SIDE_CAP, diagnostic: another side-set size, 1..2048; a
+    // small one makes searches overflow and their members take the strike pass)
+    const int efc = std::max(64, (ef_construction + 63) / 64 * 64);
+    const int sc = std::min(2048, env_int("WV_CLEANUP_SIDE_CAP", 256, 1)), xs_log2 = 9;
+    const int fixed = wv_hnsw_per_wave_words(ix->dpad, efc, sc, 0, xs_log2) - 1;
+    int vc_tbits = 0;
+    const int vc_log2 = choose_vc_log2(20 * 1024 / 4, fixed, gn, &vc_tbits);
+    const int per_wave = (wv_hnsw_per_wave_words(ix->dpad, efc, sc, vc_log2, xs_log2) + 3) & ~3;
+    int wpb = 4;
+    while (wpb > 1 && (size_t)wpb * per_wave * 4 > 160 * 1024) --wpb;
+    if ((size_t)per_wave * 4 > 160 * 1024) return fail(WV_EINVAL, "wv_index_cleanup_tombstones: LDS footprint too large");
+    // WV_BUILD_TRACE=1 (diagnostic): the phases' times, each waited for
+    const bool trace = std::getenv("WV_BUILD_TRACE") != nullptr;
+    double tph[6] = {0, 0, 0, 0, 0, 0};   // flag, search, select, sort, link, remove
+    hipEvent_t tev[3] = {};
+    if (trace)
+        for (auto& e : tev) HIP_TRY(hipEventCreate(&e));
+    auto t0 = std::chrono::steady_clock::now();
+    auto phase_done = [&](int i) -> hipError_t {
+        if (!trace) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        tph[i] += std::chrono::duration<double, std::milli>(now - t0).count();
+        t0 = now;
+        return e;
+    };
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(ix->c_bits.ensure(2 * words * 8));
+    HIP_TRY(ix->c_wave.ensure(words * 16));
+    HIP_TRY(hipMemcpyAsync(ix->c_bits.p, dead.data(), words * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ix->c_bits.as<uint64_t>() + words, skip.data(), words * 8, hipMemcpyHostToDevice, s));
+    wv::CleanupParams c{};
+    c.levels = ix->levels.as<int8_t>();
+    c.layer0 = ix->layer0.as<uint32_t>();
+    c.upper_row = ix->upper_row.as<uint32_t>();
+    c.upper = ix->upper.as<uint32_t>();
+    c.dead = ix->c_bits.as<uint64_t>();
+    c.n = gn;
+    c.deg0 = M0;
+    c.degU = M;
+    c.upper_levels = ix->upper_stride;
+    c.max_level = ix->max_level;
+    c.wave_mask = ix->c_wave.as<uint64_t>();
+    c.wave_cnt = reinterpret_cast<uint32_t*>(c.wave_mask + words);
+    c.wave_off = c.wave_cnt + words;
+    c.tomb = ix->tomb.as<uint64_t>();
+    // 1. flag: per-wave flag words and counts, a scan, the ids in ascending order
+    t0 = std::chrono::steady_clock::now();
+    HIP_TRY(wv_launch_cleanup_flag(&c, s));
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.wave_cnt, c.wave_off, (int)words, s));
+    HIP_TRY(ix->b_tmp.ensure(tb));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ix->b_tmp.p, tb, c.wave_cnt, c.wave_off, (int)words, s));
+    uint32_t last[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&last[0], c.wave_cnt + (words - 1), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&last[1], c.wave_off + (words - 1), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t nf = last[0] + last[1];
+    std::vector<uint32_t> fl(nf);
+    std::vector<int8_t> lv(gn);
+    std::vector<int32_t> st(nf, 0);
+    if (nf) {
+        HIP_TRY(ix->c_flag.ensure((size_t)nf * 4));
+        HIP_TRY(ix->c_st.ensure((size_t)nf * 4));
+        c.flagged = ix->c_flag.as<uint32_t>();
+        c.n_flagged = nf;
+        c.status = ix->c_st.as<int32_t>();
+        HIP_TRY(wv_launch_cleanup_scatter(&c, s));
+        HIP_TRY(hipMemsetAsync(ix->c_st.p, 0, (size_t)nf * 4, s));
+        HIP_TRY(hipMemcpyAsync(fl.data(), ix->c_flag.p, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(lv.data(), ix->levels.p, gn, hipMemcpyDeviceToHost, s));
+        // the link kernel's counts, read off the lists (none are kept between calls)
+        const size_t cu_words = std::max<uint64_t>(1, ix->n_upper) * (size_t)ix->upper_stride;
+        HIP_TRY(ix->b_cnt0.ensure(gn * 4));
+        HIP_TRY(ix->b_cntu.ensure(cu_words * 4));
+        HIP_TRY(hipMemsetAsync(ix->b_cnt0.p, 0, gn * 4, s));
+        HIP_TRY(hipMemsetAsync(ix->b_cntu.p, 0, cu_words * 4, s));
+        HIP_TRY(wv_launch_list_counts(ix->layer0.as<uint32_t>(), gn, M0, ix->b_cnt0.as<uint32_t>(), s));
+        HIP_TRY(wv_launch_list_counts(ix->upper.as<uint32_t>(), ix->n_upper * (uint64_t)ix->upper_stride, M,
+                                      ix->b_cntu.as<uint32_t>(), s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    HIP_TRY(phase_done(0));
+    // 2. reassign: the flagged nodes in id order, in the build's batches
+    const uint32_t bsz = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16384, n_live / batch_div));
+    std::vector<int8_t> blv(bsz);
+    for (uint32_t first = 0; first < nf; first += bsz) {
+        const int nb = (int)std::min<uint32_t>(bsz, nf - first);
+        int lb = 1;
+        for (int i = 0; i < nb; ++i) {
+            blv[i] = lv[fl[first + i]];
+            lb = std::max(lb, std::min<int>(blv[i], ix->max_level) + 1);
+        }
+        HIP_TRY(ix->b_tgt.ensure(nb));
+        HIP_TRY(ix->b_ci.ensure((size_t)nb * lb * ef_construction * 4));
+        HIP_TRY(ix->b_cd.ensure((size_t)nb * lb * ef_construction * 4));
+        HIP_TRY(ix->b_cn.ensure((size_t)nb * lb * 4));
+        const size_t nreq = (size_t)nb * lb * M0;
+        HIP_TRY(ix->b_rk.ensure(nreq * 8));
+        HIP_TRY(ix->b_rn.ensure(nreq * 4));
+        HIP_TRY(ix->b_rk2.ensure(nreq * 8));
+        HIP_TRY(ix->b_rn2.ensure(nreq * 4));
+        HIP_TRY(ix->b_uk.ensure(nreq * 8));
+        HIP_TRY(ix->b_ul.ensure(nreq * 4));
+        HIP_TRY(ix->b_uo.ensure(nreq * 4));
+        HIP_TRY(ix->b_nr.ensure(8));
+        HIP_TRY(hipMemcpyAsync(ix->b_tgt.p, blv.data(), nb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(ix->b_cn.p, 0, (size_t)nb * lb * 4, s));
+        wv::BuildParams b{};
+        wv::HnswParams& h = b.h;
+        h.X = ix->vecs.as<float>();
+        h.levels = ix->levels.as<int8_t>();
+        h.layer0 = ix->layer0.as<uint32_t>();
+        h.upper_row = ix->upper_row.as<uint32_t>();
+        h.upper = ix->upper.as<uint32_t>();
+        h.tomb = ix->c_bits.as<uint64_t>() + words;
+        h.tomb_nbits = gn;
+        h.N = gn;
+        h.entrypoint = (uint32_t)ix->entrypoint;
+        h.D = ix->dim;
+        h.ldx = ix->ldx;
+        h.ldq = ix->dpad;
+        h.metric = ix->metric;
+        h.deg0 = M0;
+        h.degU = M;
+        h.max_level = ix->max_level;
+        h.upper_levels = ix->upper_stride;
+        h.nq = nb;
+        h.ef = ef_construction;
+        h.efc = efc;
+        h.sc = sc;
+        h.vc_log2 = vc_log2;
+        h.vc_tbits = vc_tbits;
+        h.xs_log2 = xs_log2;
+        h.dpad = ix->dpad;
+        h.per_wave_words = per_wave;
+        b.nb = nb;
+        b.lb = lb;
+        b.M = M;
+        b.M0 = M0;
+        b.target = ix->b_tgt.as<int8_t>();
+        b.cand_i = ix->b_ci.as<uint32_t>();
+        b.cand_d = ix->b_cd.as<float>();
+        b.cand_n = ix->b_cn.as<int32_t>();
+        b.counts0 = ix->b_cnt0.as<uint32_t>();
+        b.countsU = ix->b_cntu.as<uint32_t>();
+        b.req_key = ix->b_rk.as<uint64_t>();
+        b.req_node = ix->b_rn.as<uint32_t>();
+        b.member = ix->c_flag.as<uint32_t>() + first;
+        b.mstatus = ix->c_st.as<int32_t>() + first;
+        b.relink = 1;
+        HIP_TRY(wv_launch_cleanup_search(&b, wpb, s));
+        HIP_TRY(phase_done(1));
+        HIP_TRY(wv_launch_cleanup_replace(&b, s));
+        HIP_TRY(phase_done(2));
+        if (trace) HIP_TRY(hipEventRecord(tev[0], s));
+        if (int rc = link_requests(ix, b, nreq, trace ? tev[1] : nullptr)) return rc;
+        if (trace) {
+            HIP_TRY(hipEventRecord(tev[2], s));
+            HIP_TRY(hipEventSynchronize(tev[2]));
+            for (int i = 0; i < 2; ++i) {
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, tev[i], tev[i + 1]));
+                tph[3 + i] += ms;
+            }
+            t0 = std::chrono::steady_clock::now();
+        }
+    }
+    // 3. strike, 4. entrypoint, 5. remove
+    uint64_t ep_key = 0;
+    const bool ep_dead = (dead[ix->entrypoint >> 6] >> (ix->entrypoint & 63)) & 1ull;
+    if (nf) {
+        HIP_TRY(wv_launch_cleanup_strike(&c, s));
+        HIP_TRY(hipMemcpyAsync(st.data(), ix->c_st.p, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (ep_dead) {
+        c.ep_blocks = wv_cleanup_entrypoint_blocks(gn);
+        HIP_TRY(ix->c_ep.ensure(((size_t)c.ep_blocks + 1) * 8));
+        c.ep_part = ix->c_ep.as<uint64_t>();
+        HIP_TRY(wv_launch_cleanup_entrypoint(&c, s));
+        HIP_TRY(hipMemcpyAsync(&ep_key, ix->c_ep.p, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(wv_launch_cleanup_remove(&c, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(phase_done(5));
+    uint64_t n_struck = 0;
+    for (int32_t v : st) n_struck += v != 0;
+    if (ep_dead && ep_key == ~0ull) {
+        ix->has_graph = false;   // resetIfEmpty: no live node is left
+    } else if (ep_dead) {
+        ix->max_level -= (int)(ep_key >> 32);
+        ix->entrypoint = (uint32_t)ep_key;
+    }
+    if (trace) {
+        for (auto& e : tev) HIP_TRY(hipEventDestroy(e));
+        std::fprintf(stderr,
+                     "[cleanup] %llu nodes, %llu live, %u flagged, %llu struck: flag %.1f search %.1f select %.1f "
+                     "sort %.1f link %.1f remove %.1f ms\n",
+                     (unsigned long long)gn, (unsigned long long)n_live, nf, (unsigned long long)n_struck, tph[0], tph[1],
+                     tph[2], tph[3], tph[4], tph[5]);
+    }
+    if (reassigned) *reassigned = nf - n_struck;
+    if (struck) *struck = n_struck;
+    return WV_OK;
+}
+
+int wv_index_cleanup_tombstones(wv_index* ix, int ef_construction, int batch_div, uint64_t* reassigned,
+                                uint64_t* removed, uint64_t* struck) {
+    if (reassigned) *reassigned = 0;
+    if (removed) *removed = 0;
+    if (struck) *struck = 0;
+    if (ef_construction < 1 || ef_construction > wv::HNSW_EF_MAX)
+        return fail(WV_EINVAL,
+                    "wv_index_cleanup_tombstones: ef_construction outside 1.." + std::to_string(wv::HNSW_EF_MAX));
+    if (batch_div < 1) return fail(WV_EINVAL, "wv_index_cleanup_tombstones: batch_div < 1");
+    if (check(ix)) return WV_EINVAL;
+    if (metric_is_l1(ix->metric)) return refuse_l1(ix, "wv_index_cleanup_tombstones");
+    std::lock_guard<std::mutex> guard(ix->mu);
+    if (!ix->has_graph || ix->gn == 0) return fail(WV_ESTATE, "wv_index_cleanup_tombstones: the index has no graph");
+    if (ix->pq_on)
+        return fail(WV_ESTATE, "wv_index_cleanup_tombstones: the index is compressed (the re-link search reads raw rows)");
+    const int M = ix->cfg.max_connections, M0 = 2 * M;
+    if (M < 2 || M0 > 256) return fail(WV_ESTATE, "wv_index_cleanup_tombstones: maxConnections out of range");
+    if (ix->deg0 != M0 || ix->degU != M)
+        return fail(WV_ESTATE, "wv_index_cleanup_tombstones: the graph's degrees (" + std::to_string(ix->deg0) + ", " +
+                                   std::to_string(ix->degU) + ") are not 2 x maxConnections and maxConnections (" +
+                                   std::to_string(M0) + ", " + std::to_string(M) + ")");
+    // D, taken once: the tombstones below graph n
+    const uint64_t gn = ix->gn, words = (gn + 63) / 64;
+    std::vector<uint64_t> dead(words), skip(words);
+    uint64_t n_dead = 0, n_live = 0;
+    for (uint64_t w = 0; w < words; ++w) {
+        const uint64_t in = w + 1 == words && (gn & 63) ? (1ull << (gn & 63)) - 1 : ~0ull;
+        dead[w] = ix->tomb_host[w] & in;
+        skip[w] = (ix->tomb_host[w] | ix->nil_host[w]) & in;
+        n_dead += (uint64_t)__builtin_popcountll(dead[w]);
+        n_live += (uint64_t)__builtin_popcountll(in & ~skip[w]);
+    }
+    if (n_dead == 0) return WV_OK;
+    HIP_TRY(hipSetDevice(ix->cfg.device));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    int rc = refresh_bitmaps(ix);   // (the device's tombstone bitmap is current before D's bits leave it)
+    if (rc) return rc;
+    // from here on lists are rewritten: a failure leaves the index without a
+    // graph (its rows are still served exactly)
+    rc = cleanup_device(ix, ef_construction, batch_div, dead, skip, n_live, reassigned, struck);
+    if (rc == WV_EINVAL) return rc;   // (its sizing check, made before the first launch)
+    if (rc) {
+        ix->has_graph = false;
+        ix->bitmaps_dirty = true;
+        return rc;
+    }
+    const bool foreign_nil = ix->any_nil && !ix->nil_cleaned;   // nil nodes of an uploaded graph stay what they were
+    // Without a graph (no live node was left) only the tombstones keep D's
+    // rows out of the flat search: they stay.
+    for (uint64_t w = 0; w < words && ix->has_graph; ++w) {
+        ix->tomb_host[w] &= ~dead[w];
+        ix->nil_host[w] |= dead[w];
+        ix->pending_host[w] &= ~dead[w];   // (a removed node is no delta row)
+    }
+    if (ix->has_graph) ix->n_tomb -= n_dead;
+    ix->any_tomb = ix->n_tomb > 0;
+    ix->nil_cleaned = !foreign_nil;
+    ix->bitmaps_dirty = true;
+    if (removed) *removed = n_dead;
+    return refresh_bitmaps(ix);
 }
 
 int wv_index_download_graph(wv_index* ix, int8_t* levels, uint32_t* layer0, uint32_t* upper_row, uint32_t* upper) {
@@ -407,9 +697,14 @@ int wv_index_download_graph(wv_index* ix, int8_t* levels, uint32_t* layer0, uint
     if (levels) HIP_TRY(hipMemcpyAsync(levels, ix->levels.p, n, hipMemcpyDeviceToHost, s));
     if (layer0) HIP_TRY(hipMemcpyAsync(layer0, ix->layer0.p, n * (size_t)ix->deg0 * 4, hipMemcpyDeviceToHost, s));
     if (upper_row) HIP_TRY(hipMemcpyAsync(upper_row, ix->upper_row.p, n * 4, hipMemcpyDeviceToHost, s));
-    if (upper && ix->max_level > 0)
+    // (the caller's level stride is max_level; the device's is wider after a cleanup lowered the top)
+    if (upper && ix->max_level > 0 && ix->upper_stride == ix->max_level)
         HIP_TRY(hipMemcpyAsync(upper, ix->upper.p, ix->n_upper * (size_t)ix->max_level * ix->degU * 4,
                                hipMemcpyDeviceToHost, s));
+    else if (upper && ix->max_level > 0 && ix->n_upper > 0)
+        HIP_TRY(hipMemcpy2DAsync(upper, (size_t)ix->max_level * ix->degU * 4, ix->upper.p,
+                                 (size_t)ix->upper_stride * ix->degU * 4, (size_t)ix->max_level * ix->degU * 4,
+                                 ix->n_upper, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return WV_OK;
 }
@@ -476,6 +771,8 @@ int wv_index_upload_graph(wv_index* ix, uint64_t n, const int8_t* levels, const 
     ix->deg0 = deg0;
     ix->degU = max_level > 0 ? degU : 1;
     ix->max_level = max_level;
+    ix->upper_stride = std::max(1, max_level);
+    ix->nil_cleaned = false;
     ix->n_upper = n_upper;
     ix->entrypoint = entrypoint;
     ix->has_graph = true;

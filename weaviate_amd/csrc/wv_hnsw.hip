@@ -1617,14 +1617,8 @@ __device__ __forceinline__ void build_search_one(const BuildParams& b, WaveState
     }
 }
 
-__global__ __launch_bounds__(256) void wv_build_search_kernel(BuildParams b) {
-    extern __shared__ float lds[];
-    const int wave = threadIdx.x >> 6;
-    const int slot = blockIdx.x * (blockDim.x >> 6) + wave;
-    if (slot >= b.nb) return;
-    const HnswParams& p = b.h;
-    float* cur = lds + (uint64_t)wave * p.per_wave_words;
-    WaveState w;
+// the wave's LDS state in the layout of wv_hnsw_per_wave_words
+__device__ __forceinline__ void build_wave_state(const HnswParams& p, float* cur, WaveState& w) {
     w.ub = nullptr;
     w.qv = cur; cur += p.dpad;
     w.Rd = cur; cur += p.efc; w.Ri = reinterpret_cast<uint32_t*>(cur); cur += p.efc;
@@ -1636,9 +1630,77 @@ __global__ __launch_bounds__(256) void wv_build_search_kernel(BuildParams b) {
     w.vc = reinterpret_cast<uint16_t*>(cur); cur += ((1 << p.vc_log2) + 1) / 2;
     w.xs = reinterpret_cast<uint32_t*>(cur); cur += (1 << p.xs_log2);
     w.ltomb = reinterpret_cast<uint32_t*>(cur);
+}
+
+__global__ __launch_bounds__(256) void wv_build_search_kernel(BuildParams b) {
+    extern __shared__ float lds[];
+    const int wave = threadIdx.x >> 6;
+    const int slot = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (slot >= b.nb) return;
+    const HnswParams& p = b.h;
+    WaveState w;
+    build_wave_state(p, lds + (uint64_t)wave * p.per_wave_words, w);
     if (p.metric == WV_METRIC_L2) build_search_one<WV_METRIC_L2>(b, w, slot);
     else if (p.metric == WV_METRIC_DOT) build_search_one<WV_METRIC_DOT>(b, w, slot);
     else build_search_one<WV_METRIC_COSINE>(b, w, slot);
+}
+
+// Tombstone cleanup (wv_index_cleanup_tombstones; reassignNeighbor,
+// delete.go:255-376): a batch of graph nodes that hold an edge to a deleted
+// node searches the graph again, each for its own vector, as
+// findAndConnectNeighbors does with the tombstones as deny list.  The graph is
+// the one before the batch, deleted nodes and the old lists included; p.tomb is
+// the deleted set, traversed through the side set and never a result, and so
+// is the member itself (a local tombstone: neighbor_connections.go:212).  A
+// layer that holds no eligible node hands its entry point on to the next.
+// status != 0 (side set or expanded-set table full): the member is not
+// re-linked.
+template <int METRIC>
+__device__ __forceinline__ void cleanup_search_one(const BuildParams& b, WaveState& w, int slot) {
+    Stamps ts;
+    const HnswParams& p = b.h;
+    const int lane = threadIdx.x & 63;
+    const int g = lane & 7;
+    const uint64_t id = b.member[slot];
+    const int target = b.target[slot];
+    for (int i = lane; i < p.dpad; i += 64) w.qv[i] = i < p.D ? p.X[id * p.ldx + i] : 0.f;
+    if (lane == 0) w.ltomb[0] = (uint32_t)id;
+    wave_sync();
+    int status = 0;
+    const int nlt = 1;
+    uint32_t n_dist = 0, n_exp = 0;
+    uint32_t ep = p.entrypoint;
+    float epd = __shfl(exact_dist_group8<METRIC>(w.qv, p.X + (uint64_t)ep * p.ldx, p.D, g), 0, 64);
+    int Rl, Sh, Sl;
+    for (int level = p.max_level; level > target; --level) {
+        search_layer<METRIC>(p, w, level, 1, ep, epd, nullptr, Rl, Sh, Sl, status, nlt, n_dist, n_exp, ts);
+        if (Rl > 0) { ep = w.Ri[0] & WV_IDMASK; epd = w.Rd[0]; }
+    }
+    for (int level = min(target, p.max_level); level >= 0; --level) {
+        search_layer<METRIC>(p, w, level, p.ef, ep, epd, nullptr, Rl, Sh, Sl, status, nlt, n_dist, n_exp, ts);
+        const uint64_t o = ((uint64_t)slot * b.lb + level) * p.ef;
+        for (int i = lane; i < Rl; i += 64) {
+            b.cand_i[o + i] = w.Ri[i] & WV_IDMASK;
+            b.cand_d[o + i] = w.Rd[i];
+        }
+        if (lane == 0) b.cand_n[(uint64_t)slot * b.lb + level] = Rl;
+        if (Rl > 0) { ep = w.Ri[0] & WV_IDMASK; epd = w.Rd[0]; }
+        wave_sync();
+    }
+    if (lane == 0) b.mstatus[slot] = status;
+}
+
+__global__ __launch_bounds__(256) void wv_cleanup_search_kernel(BuildParams b) {
+    extern __shared__ float lds[];
+    const int wave = threadIdx.x >> 6;
+    const int slot = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (slot >= b.nb) return;
+    const HnswParams& p = b.h;
+    WaveState w;
+    build_wave_state(p, lds + (uint64_t)wave * p.per_wave_words, w);
+    if (p.metric == WV_METRIC_L2) cleanup_search_one<WV_METRIC_L2>(b, w, slot);
+    else if (p.metric == WV_METRIC_DOT) cleanup_search_one<WV_METRIC_DOT>(b, w, slot);
+    else cleanup_search_one<WV_METRIC_COSINE>(b, w, slot);
 }
 
 // selectNeighborsHeuristic (heuristic.go:23-135) over n candidates sorted
@@ -1718,6 +1780,53 @@ __global__ __launch_bounds__(64) void wv_build_select_kernel(BuildParams b) {
     else build_select_one<WV_METRIC_COSINE>(b, slot, level, ci, cd, sel);
 }
 
+// Cleanup: the member's list at one level is replaced, not first written
+// (reassignNeighbor clears the connections and connects anew,
+// delete.go:357-372): the heuristic to the level's capacity (2M on layer 0),
+// the selected prefix farthest first, the rest of the row padded, the link
+// kernel's count reset, one reverse-link request per neighbour at the stride
+// M0.  A member whose search overflowed keeps its list (struck later).
+template <int METRIC>
+__device__ void cleanup_replace_one(const BuildParams& b, int slot, int level, uint32_t* ci, float* cd, uint32_t* sel) {
+    const HnswParams& p = b.h;
+    const int lane = threadIdx.x & 63;
+    const int target = b.target[slot];
+    const uint64_t id = b.member[slot];
+    const uint64_t rq = ((uint64_t)slot * b.lb + level) * b.M0;
+    for (int i = lane; i < b.M0; i += 64) b.req_key[rq + i] = ~0ull;
+    if (level > min(target, p.max_level) || b.mstatus[slot] != 0) return;
+    const int n = b.cand_n[(uint64_t)slot * b.lb + level];
+    const uint64_t o = ((uint64_t)slot * b.lb + level) * p.ef;
+    for (int i = lane; i < n; i += 64) { ci[i] = b.cand_i[o + i]; cd[i] = b.cand_d[o + i]; }
+    wave_sync();
+    const int maxc = level == 0 ? b.M0 : b.M;
+    const int ns = heuristic_select<METRIC>(p, ci, cd, n, maxc, sel);
+    uint32_t* row;
+    if (level == 0) row = const_cast<uint32_t*>(p.layer0) + id * (uint64_t)p.deg0;
+    else row = const_cast<uint32_t*>(p.upper) + ((uint64_t)p.upper_row[id] * p.upper_levels + (level - 1)) * p.degU;
+    for (int i = lane; i < maxc; i += 64) row[i] = i < ns ? sel[ns - 1 - i] : WV_NIL;
+    for (int i = lane; i < ns; i += 64) {
+        b.req_key[rq + i] = ((uint64_t)level << 32) | sel[i];
+        b.req_node[rq + i] = (uint32_t)id;
+    }
+    if (lane == 0) {
+        if (level == 0) b.counts0[id] = ns;
+        else b.countsU[(uint64_t)p.upper_row[id] * p.upper_levels + (level - 1)] = ns;
+    }
+}
+
+__global__ __launch_bounds__(64) void wv_cleanup_replace_kernel(BuildParams b) {
+    extern __shared__ float lds[];
+    const int slot = blockIdx.x / b.lb, level = blockIdx.x % b.lb;
+    if (slot >= b.nb) return;
+    uint32_t* ci = reinterpret_cast<uint32_t*>(lds);
+    float* cd = lds + b.h.ef;
+    uint32_t* sel = reinterpret_cast<uint32_t*>(lds + 2 * b.h.ef);
+    if (b.h.metric == WV_METRIC_L2) cleanup_replace_one<WV_METRIC_L2>(b, slot, level, ci, cd, sel);
+    else if (b.h.metric == WV_METRIC_DOT) cleanup_replace_one<WV_METRIC_DOT>(b, slot, level, ci, cd, sel);
+    else cleanup_replace_one<WV_METRIC_COSINE>(b, slot, level, ci, cd, sel);
+}
+
 // connectNeighborAtLevel for every new link of one neighbour, in batch order.
 template <int METRIC>
 __device__ void build_link_one(const BuildParams& b, int r, uint32_t* ci, float* cd, uint32_t* ui, float* ud,
@@ -1748,6 +1857,11 @@ __device__ void build_link_one(const BuildParams& b, int r, uint32_t* ci, float*
     const uint32_t off = b.run_off[r], len = b.run_len[r];
     for (uint32_t t = 0; t < len; ++t) {
         const uint32_t x = b.sorted_node[off + t];
+        if (b.relink) {   // a graph node links again: the neighbour may hold it already
+            bool held = false;
+            for (int i = lane; i < c; i += 64) held = held || rowl[i] == x;
+            if (__any(held)) continue;
+        }
         if (c < maxc) {   // appendConnectionAtLevelNoLock (:151-157)
             if (lane == 0) rowl[c] = x;
             c++;
@@ -1888,6 +2002,28 @@ hipError_t wv_launch_build_select(const wv::BuildParams* b, hipStream_t s) {
     const size_t lds = (2 * (size_t)b->h.ef + b->M) * sizeof(float);
     if (b->nb == 0) return hipSuccess;
     hipLaunchKernelGGL(wv::wv_build_select_kernel, dim3((unsigned)(b->nb * b->lb)), dim3(64), lds, s, *b);
+    return hipGetLastError();
+}
+
+// the cleanup's batch: members re-linked from the graph as it stands (a side
+// set and one local tombstone in the wave state, unlike the build's)
+hipError_t wv_launch_cleanup_search(const wv::BuildParams* b, int waves_per_block, hipStream_t s) {
+    if (b->nb == 0) return hipSuccess;
+    if (!b->member || !b->mstatus || !b->h.tomb || b->h.sc < 1 || b->h.xs_log2 < 1 || waves_per_block < 1 ||
+        waves_per_block > 4)
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)waves_per_block * b->h.per_wave_words * sizeof(float);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((b->nb + waves_per_block - 1) / waves_per_block);
+    hipLaunchKernelGGL(wv::wv_cleanup_search_kernel, dim3(blocks), dim3(64 * waves_per_block), lds, s, *b);
+    return hipGetLastError();
+}
+
+hipError_t wv_launch_cleanup_replace(const wv::BuildParams* b, hipStream_t s) {
+    if (b->nb == 0) return hipSuccess;
+    if (!b->member || !b->mstatus) return hipErrorInvalidValue;
+    const size_t lds = (2 * (size_t)b->h.ef + b->M0) * sizeof(float);
+    hipLaunchKernelGGL(wv::wv_cleanup_replace_kernel, dim3((unsigned)(b->nb * b->lb)), dim3(64), lds, s, *b);
     return hipGetLastError();
 }
 

@@ -130,7 +130,11 @@ struct wv_index {
     bool has_graph = false;
     uint64_t gn = 0;
     int deg0 = 0, degU = 0, max_level = 0;
+    int upper_stride = 1;   // level stride of `upper`: max(1, max_level), or the older top's after a cleanup lowered it
     uint64_t n_upper = 0, entrypoint = 0;
+    // every nil node below gn was made by wv_index_cleanup_tombstones (no list
+    // names one: searches and wv_index_extend_graph never meet them)
+    bool nil_cleaned = false;
     std::vector<uint64_t> nil_host;   // graph nil nodes and ids >= gn, one bit per id
     DevBuf levels, layer0, upper_row, upper;
     // bitmaps
@@ -180,6 +184,10 @@ struct wv_index {
     DevBuf delta, dmask, dl_ids, dl_d, dl_n, dq_tmp;
     // graph construction scratch
     DevBuf b_tgt, b_ci, b_cd, b_cn, b_cnt0, b_cntu, b_rk, b_rn, b_rk2, b_rn2, b_uk, b_ul, b_uo, b_nr, b_tmp;
+    // tombstone cleanup: the deleted set (and that set with the nil nodes), the
+    // flag pass's words per wave, the flagged ids, their search status, the
+    // entrypoint reduction's keys
+    DevBuf c_bits, c_wave, c_flag, c_st, c_ep;
     // product quantization: h.pq / h.compressed
     // (compress.go:39-89).  Codes live on the device as u8 (ks <= 256) or u16
     // per segment, rows padded to whole words; has_code marks rows encoded.

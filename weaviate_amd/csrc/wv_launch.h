@@ -31,6 +31,14 @@ hipError_t wv_launch_build_link(const wv::BuildParams* b, hipStream_t s);
 hipError_t wv_launch_list_counts(const uint32_t* lists, uint64_t n_lists, int deg, uint32_t* counts, hipStream_t s);
 hipError_t wv_launch_upper_relay(const uint32_t* old_upper, const uint32_t* old_counts, uint64_t n_rows, int old_levels,
                                  int new_levels, int deg, uint32_t* new_upper, uint32_t* new_counts, hipStream_t s);
+hipError_t wv_launch_cleanup_search(const wv::BuildParams* b, int waves_per_block, hipStream_t s);
+hipError_t wv_launch_cleanup_replace(const wv::BuildParams* b, hipStream_t s);
+hipError_t wv_launch_cleanup_flag(const wv::CleanupParams* c, hipStream_t s);
+hipError_t wv_launch_cleanup_scatter(const wv::CleanupParams* c, hipStream_t s);
+hipError_t wv_launch_cleanup_strike(const wv::CleanupParams* c, hipStream_t s);
+hipError_t wv_launch_cleanup_entrypoint(const wv::CleanupParams* c, hipStream_t s);
+hipError_t wv_launch_cleanup_remove(const wv::CleanupParams* c, hipStream_t s);
+int wv_cleanup_entrypoint_blocks(uint64_t n);
 int wv_hnsw_per_wave_words(int dpad, int efc, int sc, int vc_log2, int xs_log2);
 int wv_hnsw_side_per_wave_words(int dpad, int side_rows, int vc_log2, int xs_log2);
 int wv_hnsw_reg_per_wave_words(int dpad, int vc_log2);

@@ -858,10 +858,20 @@ int wv_mirror_compact(wv_mirror* m) {
     // rows added, not for all of them); where only a rebuild applies -- no
     // graph yet, deleted nodes in it, other degrees -- the whole graph is built
     int rc = WV_ESTATE;
-#ifndef WV_TSAN_BUILD   // (the ThreadSanitizer build's CPU index has no such entry point)
+    bool cleaned = false;
+#ifndef WV_TSAN_BUILD   // (the ThreadSanitizer build's CPU index has no such entry points)
+    if (m->opt.cleanup_on_compact) {
+        // deleted nodes leave the graph first, so that it can be extended; a
+        // graph that cannot be cleaned (WV_ESTATE) is rebuilt as before
+        uint64_t removed = 0;
+        rc = wv_index_cleanup_tombstones(m->ix, m->opt.ef_construction, 32, nullptr, &removed, nullptr);
+        if (rc && rc != WV_ESTATE) return rc;
+        cleaned = rc == WV_OK && removed > 0;
+    }
     rc = wv_index_extend_graph(m->ix, m->opt.ef_construction, m->opt.build_seed, 32, nullptr);
 #endif
-    if (rc == WV_ESTATE) rc = wv_index_build_graph(m->ix, m->opt.ef_construction, m->opt.build_seed, 32);
+    // (after a cleanup a rebuild would insert the removed rows again: the delta keeps serving)
+    if (rc == WV_ESTATE && !cleaned) rc = wv_index_build_graph(m->ix, m->opt.ef_construction, m->opt.build_seed, 32);
     if (rc) return rc;   // e.g. holes below n_rows: the delta keeps serving exactly
     uint64_t n = 0;
     wv_index_graph_info(m->ix, &n, nullptr, nullptr, nullptr, nullptr, nullptr);

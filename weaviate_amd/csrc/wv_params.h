@@ -764,6 +764,32 @@ struct BuildParams {
     const uint32_t* run_len;
     const uint32_t* sorted_node;
     int n_runs;
+    // tombstone cleanup (wv_index_cleanup_tombstones): the batch's members are
+    // graph nodes that search for themselves again; null / 0 in the build
+    const uint32_t* member;   // [nb] ids of the batch, ascending (requests have the stride M0 there)
+    int32_t* mstatus;         // [nb] the member's search status (non-zero: not re-linked, struck instead)
+    int relink;               // link kernel: a link the neighbour already holds is skipped
+};
+
+// Tombstone cleanup outside the searches (wv_graph_cleanup.hip).  dead: the
+// bitmap of D, the tombstoned ids below n, taken once at entry.
+struct CleanupParams {
+    int8_t* levels;
+    uint32_t* layer0;
+    const uint32_t* upper_row;
+    uint32_t* upper;
+    const uint64_t* dead;
+    uint64_t n;               // graph nodes
+    int deg0, degU, upper_levels, max_level;
+    uint64_t* wave_mask;      // flag pass: one flag bit per node, a word per wave's 64 nodes
+    uint32_t* wave_cnt;       //   ... its popcount, and after the scan its offset in `flagged`
+    uint32_t* wave_off;
+    uint32_t* flagged;        // the flagged ids, ascending
+    uint32_t n_flagged;
+    const int32_t* status;    // [n_flagged] strike pass: non-zero entries are struck
+    uint64_t* tomb;           // remove pass: the index's tombstone bitmap (D's bits cleared)
+    uint64_t* ep_part;        // entrypoint reduction: a key per block, then the result in [0]
+    int ep_blocks;
 };
 
 }  // namespace wv

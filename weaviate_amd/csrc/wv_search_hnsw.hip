@@ -41,7 +41,7 @@ wv::HnswParams hnsw_params(wv_index* ix, const Batch& b, int ef, int efc) {
     hp.deg0 = ix->deg0;
     hp.degU = ix->degU;
     hp.max_level = ix->max_level;
-    hp.upper_levels = ix->max_level;
+    hp.upper_levels = ix->upper_stride;
     hp.nq = b.nq;
     hp.k = b.k;
     hp.ef = ef;

@@ -178,6 +178,18 @@ class GPUVectorIndex:
         check(lib().wv_index_extend_graph(self._h, ef_construction, seed, batch_div, C.byref(k)))
         return k.value
 
+    def cleanup_tombstones(self, ef_construction: int = 128, batch_div: int = 32) -> dict:
+        """Remove the tombstoned nodes from the graph on the GPU
+        (wv_index_cleanup_tombstones): every node with an edge to one is
+        re-linked, the entrypoint replaced if it was deleted, the nodes become
+        nil and their tombstones are dropped.  Returns the counts `reassigned`,
+        `removed` and `struck` (nodes whose search overflowed: their dead edges
+        were cut, not replaced)."""
+        r, d, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().wv_index_cleanup_tombstones(self._h, ef_construction, batch_div, C.byref(r), C.byref(d),
+                                                C.byref(k)))
+        return dict(reassigned=r.value, removed=d.value, struck=k.value)
+
     def query_ld(self) -> int:
         """Row stride (floats) of the device query rows search_batch_device reads."""
         return lib().wv_index_query_ld(self._h)

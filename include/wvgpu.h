@@ -66,7 +66,8 @@ typedef enum {
  * wv_search_by_vector_distance* work as for the other metrics.  Refused with
  * WV_ESTATE: the graph (wv_index_upload_graph, _build_graph, _extend_graph)
  * and the quantizer (wv_index_set_pq, _fit_pq, wv_index_set_compressed(ix, 1)).
- * wv_search_batch_ids answers every query through its bitmap route.
+ * wv_search_batch_ids and wv_search_by_vector_distance_batch_ids walk the
+ * lists with a kernel of these metrics' own, which reads only the listed rows.
  * wv_mirror_create and wv_group_create reject these metrics with WV_EINVAL:
  * mirror, group and the Go constants are follow-ups. */
 typedef enum { WV_L2_SQUARED = 0, WV_DOT = 1, WV_COSINE_DOT = 2, WV_MANHATTAN = 3, WV_HAMMING = 4 } wv_metric;
@@ -364,7 +365,8 @@ int wv_search_by_vector_distance_batch(wv_index *ix, const float *queries, int n
  * and, on an index that is not compressed, vectors wider than 8192 floats
  * take the per-query wv_search_by_vector_distance over a bitmap row built for
  * that query alone.  A PQ-compressed index walks the lists over its codes
- * (switches: wv_search_by_vector_distance_batch).  Not provided: a group variant
+ * (switches: wv_search_by_vector_distance_batch), a manhattan or hamming
+ * index with a list kernel of those metrics.  Not provided: a group variant
  * (wv_group_search_by_vector_distance_batch takes bitmaps only) and a
  * device-pointer variant. */
 int wv_search_by_vector_distance_batch_ids(wv_index *ix, const float *queries, int nq, const float *target_distances,
@@ -432,7 +434,11 @@ int wv_search_batch(wv_index *ix, const float *queries, int nq, int k, int ef, c
  * bitmap rows built on the device.  On a PQ-compressed index the flat queries
  * take the bitmap route too unless wv_index_set_pq_list_search is on: then the
  * list kernel walks the listed rows' codes, with the PQ distance of the
- * index's searches, under the same conditions (any dimension).
+ * index's searches, under the same conditions (any dimension).  A manhattan
+ * or hamming index has a sparse kernel of its own under the uncompressed
+ * index's conditions: k <= 256 there too, where the unfiltered search of such
+ * an index serves k <= 128 from its tile kernel; it has no graph, so AUTO
+ * searches every list flat.
  * WV_FLAT_IDS_PQ_LUT=0|1, read per call: that kernel evaluates rows directly /
  * from the per-query lookup table wherever it fits (unset: the table where a
  * workgroup's chunk of the list holds at least `centroids` ids); for tests and

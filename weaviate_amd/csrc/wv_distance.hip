@@ -628,7 +628,7 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
         hipStream_t s = ix->stream;
         N = ix->n_rows;
         ix->sbd_ids_list_q = ix->sbd_ids_list_ids = ix->sbd_ids_hnsw_q = ix->sbd_ids_legacy_q = 0;
-        if (ix->pq_on ? !sbd_pq_enabled() : ix->dpad > wv::FLAT_IDS_DPAD_MAX || metric_is_l1(ix->metric)) {
+        if (ix->pq_on ? !sbd_pq_enabled() : ix->dpad > wv::FLAT_IDS_DPAD_MAX) {
             // the uncompressed kernel keeps the query row in LDS (the
             // compressed ones read it from memory): the per-query path
             for (int q = 0; q < nq; ++q) legacy.push_back(q);
@@ -704,7 +704,7 @@ int wv_search_by_vector_distance_batch_ids(wv_index* ix, const float* queries, i
                         pp.lut = sbd_pq_lut();
                         HIP_TRY(wv_launch_sbd_pq_ids(&pp, s));
                     } else {
-                        HIP_TRY(wv_launch_sbd_ids(&sp, s));
+                        HIP_TRY(metric_is_l1(ix->metric) ? wv_launch_l1_sbd_ids(&sp, s) : wv_launch_sbd_ids(&sp, s));
                     }
                     HIP_TRY(wv_sbd_ids_sort(sp.keys, ix->sbd_tmp.as<unsigned long long>(), n_keys, sp.cnt, q0, nqc,
                                             sp.seg_beg, sp.seg_cap, ix->sbd_seg.as<int>() + 2 * nqc, &ix->sbd_scr,

@@ -1,5 +1,5 @@
 // wv_fi_select.h -- the (dist, id) selection the flat kernels that walk rows
-// one per lane share (wv_flat_ids.hip, wv_pq_scan.hip).  Keys are fin_key
+// one per lane share (wv_flat_ids.hip, wv_pq_scan.hip, wv_l1_ids.hip).  Keys are fin_key
 // keys: a wave holds its 256 smallest sorted in registers (element 64 j + lane
 // in register j); a new key is staged only if it is below the wave's k-th, and
 // a full stage is sorted and merged in (the element-wise minimum of an
@@ -104,5 +104,34 @@ __device__ __forceinline__ void fi_write(const P& p, const uint64_t (&top)[4], i
         n += __popcll(__ballot(has));
     }
     if (lane == 0) p.out_n[q] = n;
+}
+
+// The end of a workgroup's walk: each wave's last staged keys flushed, the
+// waves merged through their stages, and wave 0 writes the query's output rows
+// (one chunk) or the chunk's sorted keys for flat_ids_merge_kernel.
+template <int METRIC, class P>
+__device__ __forceinline__ void fi_finish(const P& p, uint64_t (&top)[4], uint64_t* stage_all, uint64_t* stage, int cnt,
+                                          int s, int chunk, int q, int lane, int wave) {
+    if (cnt) fi_flush(top, stage, cnt, lane);
+    fi_wave_sync();
+    // the waves of the workgroup: each leaves its sorted keys in its stage
+#pragma unroll
+    for (int j = 0; j < 4; ++j) stage[64 * j + lane] = top[j];
+    __syncthreads();
+    if (wave != 0) return;
+    for (int w = 1; w < 4; ++w) {
+        uint64_t od[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) od[j] = stage_all[w * FI_STAGE + 255 - (64 * j + lane)];
+        fi_merge(top, od, lane);
+    }
+    if (p.n_chunks == 1) {
+        fi_write<METRIC>(p, top, q, lane);
+    } else {
+        unsigned long long* out = p.part + ((size_t)s * p.n_chunks + chunk) * p.k;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (64 * j + lane < p.k) out[64 * j + lane] = top[j];
+    }
 }
 }  // namespace wv

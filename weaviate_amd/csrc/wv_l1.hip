@@ -70,6 +70,7 @@
 //
 // Built without the packed fp32 forms, as wv_sbd_h16.hip is.
 #include "wv_device.h"
+#include "wv_l1_dev.h"
 #include "wv_launch.h"
 #include "wv_params.h"
 #include "wv_topk.h"
@@ -83,11 +84,7 @@ enum { L1_KNN = 0, L1_THRESH = 1 };
 
 static_assert(L1_KMAX + L1_BN <= L1_POOL, "a pruned pool takes one more tile");
 
-template <int METRIC>
-__device__ __forceinline__ void l1_step(float& acc, float q, float x) {
-    if (METRIC == WV_METRIC_MANHATTAN) acc += fabsf(q - x);
-    else acc += q != x ? 1.f : 0.f;
-}
+// l1_step, l1_load4: wv_l1_dev.h
 
 // word w of a bitmap of nbits bits: bits past nbits (and words past it) read 0
 __device__ __forceinline__ uint64_t l1_word(const uint64_t* __restrict__ bits, uint64_t nbits, uint64_t w) {
@@ -95,17 +92,6 @@ __device__ __forceinline__ uint64_t l1_word(const uint64_t* __restrict__ bits, u
     if (w >= words) return 0;
     uint64_t v = bits[w];
     if (w == words - 1 && (nbits & 63)) v &= (1ull << (nbits & 63)) - 1;
-    return v;
-}
-
-// float4 at column kk of a row of ld floats (null row: zeros), columns >= D zeroed
-__device__ __forceinline__ float4 l1_load4(const float* __restrict__ row, int kk, int ld, int D) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row && kk < ld) v = *reinterpret_cast<const float4*>(row + kk);
-    if (kk + 0 >= D) v.x = 0.f;
-    if (kk + 1 >= D) v.y = 0.f;
-    if (kk + 2 >= D) v.z = 0.f;
-    if (kk + 3 >= D) v.w = 0.f;
     return v;
 }
 

@@ -101,6 +101,8 @@ hipError_t wv_launch_ids_to_bits(const uint32_t* ids, const uint64_t* off, const
                                  uint64_t max_len, uint64_t n_rows, uint64_t words, uint64_t* bits, hipStream_t s);
 hipError_t wv_launch_l1_knn(const wv::L1Params* p, hipStream_t s);
 hipError_t wv_launch_l1_thresh(const wv::L1Params* p, hipStream_t s);
+hipError_t wv_launch_l1_ids(const wv::FlatIdsParams* p, hipStream_t s);
+hipError_t wv_launch_l1_sbd_ids(const wv::SbdIdsParams* p, hipStream_t s);
 hipError_t wv_launch_pq_topk(const float* skey, const uint32_t* sval, const float* dist, const uint32_t* rows,
                              uint64_t nr, int q0, int nqc, int k, uint64_t id_base, uint64_t* out_ids, float* out_d,
                              int32_t* out_n, hipStream_t s);

@@ -604,6 +604,17 @@ struct FlatIdsParams {
 };
 constexpr int FLAT_IDS_DPAD_MAX = 8192;   // the query row lives in LDS
 
+// The same walks on a manhattan or hamming index (wv_l1_ids.hip): FlatIdsParams
+// for the k-NN epilogue, SbdIdsParams (never the candidate form) for the
+// threshold one.  A lane owns L1I_R of the 64 L1I_R list entries a wave takes
+// a step, i.e. L1I_R independent serial chains.
+#ifndef WV_L1_IDS_R
+#define WV_L1_IDS_R 2   // (measured against 1 and 4 in A/B builds: profiles/l1_ids/README.md)
+#endif
+constexpr int L1I_R = WV_L1_IDS_R;
+constexpr int L1I_STEP = 64 * L1I_R;      // list entries per wave step
+constexpr int L1I_LD = L1I_STEP + 4;      // floats of a ring row: 4 LD = 16 mod 64 banks
+
 // Flat search over per-query id lists on a compressed index (wv_flat_ids.hip,
 // flat_ids_pq_kernel): FlatIdsParams' lists, selection and outputs, the
 // distance from the codes (pq_dist_row's bits, from the workgroup's lookup

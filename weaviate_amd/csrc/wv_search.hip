@@ -385,7 +385,8 @@ int wv_search_batch(wv_index* ix, const float* queries, int nq, int k, int ef, c
 // rule of search.go:64-79 is applied on the host from each list's length; a
 // flat query whose list is short goes to the sparse kernel (wv_flat_ids.hip;
 // on a compressed index its PQ variant, where wv_index_set_pq_list_search is
-// on), every other query to search_core over bitmap rows scattered on the device.
+// on; on a manhattan or hamming index wv_l1_ids.hip), every other query to
+// search_core over bitmap rows scattered on the device.
 int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int ef, const uint64_t* allow_ids,
                         const uint64_t* allow_offsets, int mode, uint64_t* out_ids, float* out_dists, int32_t* out_n) {
     if (nq < 0) return fail(WV_EINVAL, "wv_search_batch_ids: nq < 0");
@@ -431,8 +432,9 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
         const bool can_hnsw = ix->has_graph && ef_eff <= wv::HNSW_EF_MAX;
         // (compressed: the list kernel over the codes, where the index asks
         // for it -- its query row stays in memory, so any dimension)
-        // (manhattan, hamming: no list kernel, every query by its bitmap row)
-        const bool sparse_ok = k <= wv::BF_WIDE_KMAX && !metric_is_l1(ix->metric) &&
+        // (manhattan, hamming: their own list kernel, wv_l1_ids.hip -- no
+        // graph on such an index, so AUTO searches every list flat)
+        const bool sparse_ok = k <= wv::BF_WIDE_KMAX &&
                                (ix->pq_on ? ix->pq_list_search : ix->dpad <= wv::FLAT_IDS_DPAD_MAX);
         std::vector<int32_t> sel[3];   // sparse, bitmap rows searched flat, bitmap rows searched by HNSW
         uint64_t sp_ids = 0, sp_max = 0;
@@ -508,7 +510,7 @@ int wv_search_batch_ids(wv_index* ix, const float* queries, int nq, int k, int e
                 fp.X = ix->vecs.as<float>();
                 fp.D = ix->dim;
                 fp.ldx = ix->ldx;
-                HIP_TRY(wv_launch_flat_ids(&fp, s));
+                HIP_TRY(metric_is_l1(ix->metric) ? wv_launch_l1_ids(&fp, s) : wv_launch_flat_ids(&fp, s));
             }
             if (ix->timing) {
                 HIP_TRY(hipEventRecord(ix->fi_ev[1], s));

@@ -424,7 +424,8 @@ class GPUVectorIndex:
         """search_by_vector_distance_batch with one allow list per query given
         as ids (a sequence of nq integer arrays, each strictly ascending): the
         threshold pass walks only the listed rows and no bitmap is built on the
-        host (wv_search_by_vector_distance_batch_ids).  Same result."""
+        host (wv_search_by_vector_distance_batch_ids).  Same result.  Every
+        metric has its list kernel, manhattan and hamming included."""
         qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         nq = qs.shape[0]
         ts = np.ascontiguousarray(np.broadcast_to(np.asarray(targets, np.float32), (nq,)))
@@ -489,7 +490,9 @@ class GPUVectorIndex:
         """search_batch with one allow list per query given as ids (a sequence
         of nq integer arrays, each strictly ascending; the AllowList's Slice()):
         short lists are searched by walking only the listed rows
-        (wv_search_batch_ids).  Same result as search_batch."""
+        (wv_search_batch_ids).  Same result as search_batch.  On a manhattan
+        or hamming index every list is walked that way for k <= 256 (in "exact"
+        mode: a list shorter than an eighth of the rows)."""
         qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         nq = qs.shape[0]
         flat, off = self._id_lists(allow_ids, nq)

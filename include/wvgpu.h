@@ -63,6 +63,8 @@ typedef enum {
  * plain index only, and only flat: every search of such an index is the exact
  * one (WV_MODE_AUTO and WV_MODE_EXACT; WV_MODE_HNSW is WV_ESTATE), with
  * distances bit-identical to the reference's and rows ordered by (dist, id).
+ * k <= 128 is one tiled kernel; larger k is a scan and sort per query, or, up
+ * to k = 4096 with wv_index_set_large_k on, the batched large-k route.
  * wv_search_by_vector_distance* work as for the other metrics.  Refused with
  * WV_ESTATE: the graph (wv_index_upload_graph, _build_graph, _extend_graph)
  * and the quantizer (wv_index_set_pq, _fit_pq, wv_index_set_compressed(ix, 1)).
@@ -472,28 +474,34 @@ int wv_index_set_pq_scan(wv_index *ix, int on);
  * over PQ codes answered by the fused scan and by the sort route.  Both are 0
  * after a search that ran no such flat search. */
 int wv_last_pq_scan_stats(wv_index *ix, uint64_t *fused_queries, uint64_t *sorted_queries);
-/* Flat k-NN with k past every key pass on an uncompressed l2-squared, dot or
- * cosine-dot index -- k > 256, or k > 32 with per-query bitmaps, on the delta
- * rows of a mutable index or without an f16 image -- by the batched large-k
- * route (on), for k <= 4096 and dim <= 1024.  A bound pass ranks every
+/* Flat k-NN with k past every key pass by the batched large-k route (on), for
+ * k <= 4096.  Which k that is depends on the index kind: on an uncompressed
+ * l2-squared, dot or cosine-dot index (dim <= 1024) k > 256, or k > 32 with
+ * per-query bitmaps, on the delta rows of a mutable index or without an f16
+ * image; on a manhattan or hamming index (dim <= 8192, fewer than 2^31 rows)
+ * k > 128; on a compressed index (any dim; ranked by the PQ distance, as every
+ * flat search there) each k > 32 that the fused scan does not serve: k > 256
+ * with wv_index_set_pq_scan on, k > 32 with it off.  A bound pass ranks every
  * (k / 16)-th row per query and takes the 36th smallest distance, tau: the
  * sample holds 16 of the k nearest on average, so tau lies below the true k-th
  * distance for about one query in 1e5, and 2.25 k rows lie within it on
- * average.  The distance search's threshold pass (the f16 filter where
- * wv_index_set_sbd_key_pass is on) lists every eligible row within tau, a
- * segmented sort orders the lists, and the first k of each are the answer.  A
- * query whose list outgrew WV_SBD_CAP entries, holds fewer than k rows within
- * tau, or (f16 filter) has too few sampled rows for a finite tau is answered by
- * the per-query route; so is every query when the route is off (the default),
- * on a compressed, manhattan or hamming index, for larger k or dim, inside a
- * distance batch, and for the smallest batches, where one long list's sort
- * costs more than the query's scan (one query with k > 600, two or three with
- * k > 2000: profiles/large_k/README.md).  The answers are the same bits either way: reference-order
- * distances, (dist, id) order.  Queries run in chunks of at most
- * WV_BIGK_MAX_ENTRIES (2^26, read per call) list entries, one stream sync per
- * chunk.  (Off by default because the suite pins the per-query route's
- * fallback counts; making on the library default is a follow-up.)  A null
- * index returns WV_EINVAL. */
+ * average.  The distance search's threshold pass of the index kind (the f16
+ * filter where wv_index_set_sbd_key_pass is on) lists every eligible row
+ * within tau, a segmented sort orders the lists, and the first k of each are
+ * the answer.  A query whose list outgrew WV_SBD_CAP entries, holds fewer than
+ * k rows within tau, or (f16 filter) has too few sampled rows for a finite tau
+ * is answered by the per-query route (on a compressed index: the sort route,
+ * counted in wv_last_pq_scan_stats as sorted); so is every query when the
+ * route is off (the default), for larger k or dim, inside a distance batch,
+ * and for the smallest uncompressed batches, where one long list's sort costs
+ * more than the query's scan (one query with k > 600 -- a single hamming query
+ * at every k -- two or three with k > 2000: profiles/large_k/README.md,
+ * profiles/large_k_kinds/README.md; a compressed index has no such cut-off).
+ * The answers are the same bits either way: reference-order distances,
+ * (dist, id) order.  Queries run in chunks of at most WV_BIGK_MAX_ENTRIES
+ * (2^26, read per call) list entries, one stream sync per chunk.  (Off by
+ * default because the suite pins the per-query route's fallback counts; making
+ * on the library default is a follow-up.)  A null index returns WV_EINVAL. */
 int wv_index_set_large_k(wv_index *ix, int on);
 /* The last search on the index (nullable outputs): the queries the large-k
  * route answered from their lists and those it handed to the per-query route.

@@ -24,33 +24,17 @@
 // bigk_tau_kernel, one workgroup per query, merges the segments the same way
 // and writes the BIGK_RANK-th smallest as tau, +inf where the sample holds
 // fewer finite distances -- then every eligible row is listed.
+//
+// The bound pass here is the uncompressed l2 / dot / cosine one; compressed,
+// manhattan and hamming indexes have theirs in wv_bigk_kinds.hip, and share
+// the keys, the wave merge (wv_bigk_dev.h), bigk_tau_kernel and the emit.
+#include "wv_bigk_dev.h"
 #include "wv_device.h"
 #include "wv_launch.h"
 #include "wv_params.h"
 #include "wv_topk.h"
 
 namespace wv {
-
-constexpr uint32_t BIGK_EMPTY = 0xFFFFFFFFu;
-constexpr uint32_t BIGK_KEY_INF = 0xFF800000u;   // bigk_key(+inf)
-
-// the distance's half of sbd_key: unsigned order = float order, -0 and +0 one key
-__device__ __forceinline__ uint32_t bigk_key(float d) { return (uint32_t)(sbd_key(d, 0u) >> 32); }
-__device__ __forceinline__ float bigk_unkey(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-// the workgroup's four sorted lists into wave 0's (wl: [4][64]); the other
-// waves' return value is their own list
-__device__ __forceinline__ uint32_t bigk_merge_waves(uint32_t top, uint32_t (*wl)[64], int wave, int lane) {
-    wl[wave][lane] = top;
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) top = wave_min64_of(top, wl[w][lane], lane);
-    }
-    return top;
-}
 
 template <int METRIC>
 __global__ __launch_bounds__(256) void bigk_bound_kernel(BigkParams p) {
@@ -155,13 +139,22 @@ hipError_t wv_launch_bigk_bound(const wv::BigkParams* p, hipStream_t s) {
     else hipLaunchKernelGGL(wv::bigk_bound_kernel<WV_METRIC_COSINE>, grid, dim3(256), 0, s, *p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return wv_launch_bigk_tau(p, s);
+}
+
+// every query's tau from its segments' keys (any bound pass's second half)
+hipError_t wv_launch_bigk_tau(const wv::BigkParams* p, hipStream_t s) {
+    if (p->nq == 0) return hipSuccess;
+    if (p->n_seg < 1 || !p->seg_keys || !p->tau) return hipErrorInvalidValue;
     hipLaunchKernelGGL(wv::bigk_tau_kernel, dim3((unsigned)p->nq), dim3(256), 0, s, *p);
     return hipGetLastError();
 }
 
+// (a zero distance is -0 only under the dot metrics' wrap, raw or PQ; the
+// manhattan and hamming sums are never negative)
 hipError_t wv_launch_bigk_emit(const wv::BigkParams* p, hipStream_t s) {
     if (p->nq == 0) return hipSuccess;
-    if (p->metric > WV_METRIC_COSINE || p->k < 1 || p->cap < 1 || !p->sorted || !p->cnt || !p->tau || !p->flag)
+    if (p->metric > WV_METRIC_HAMMING || p->k < 1 || p->cap < 1 || !p->sorted || !p->cnt || !p->tau || !p->flag)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)p->nq);
     if (p->metric == WV_METRIC_DOT) hipLaunchKernelGGL(wv::bigk_emit_kernel<WV_METRIC_DOT>, grid, dim3(256), 0, s, *p);

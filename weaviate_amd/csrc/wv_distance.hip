@@ -29,7 +29,6 @@ bool sbd_pq_enabled() {
     const char* e = std::getenv("WV_SBD_PQ");
     return !(e && e[0] == '0' && !e[1]);
 }
-int sbd_pq_lut() { return env_tri("WV_SBD_PQ_LUT"); }
 
 // A batch here keeps its lists and counts in the ix->sbd_* buffers while its
 // round 1 runs k-NN searches on the same stream: marked, so that the large-k
@@ -83,6 +82,53 @@ namespace wv_host {
 
 // entries of a query's list (WV_SBD_CAP, read per call)
 int sbd_cap() { return env_int("WV_SBD_CAP", wv::SBD_CAP, 128); }
+
+int sbd_pq_lut() { return env_tri("WV_SBD_PQ_LUT"); }
+
+// The threshold pass of the index kinds that have one of their own -- over the
+// codes of a compressed index (wv_sbd_pq.hip), the tiled kernel's threshold
+// epilogue on a manhattan or hamming one (wv_l1.hip) -- for the staged batch
+// sp (queries, targets, bitmaps, lists and counts set; rows_per_block the
+// scan's).  The distance batches and the large-k route launch it from here.
+bool sbd_kind_has_pass(const wv_index* ix) { return ix->pq_on || metric_is_l1(ix->metric); }
+int sbd_kind_pass(wv_index* ix, const wv::SbdParams& sp, hipStream_t s) {
+    if (ix->pq_on) {
+        wv::SbdPqParams pp{};
+        pp.pq = pq_params(ix);
+        pp.lut = sbd_pq_lut();
+        pp.s = sp;
+        // A workgroup that builds the table reads ks * D centroid
+        // floats, 4 ks ds bytes a segment, against the m code bytes of
+        // each row: from 4 ks ds rows a block the table's traffic is at
+        // most the block's code traffic (and its ks * D multiply-adds
+        // at most a quarter of its rows' m gathers), so that is the
+        // floor where it exceeds 4096 (ks 256, ds 4: the same 4096).
+        const uint64_t lut_floor = 4 * (uint64_t)pp.pq.ks * (uint64_t)pp.pq.ds;
+        if (pp.lut != 0 && (uint64_t)pp.pq.m * pp.pq.ks * 4 <= (uint64_t)wv::SBD_PQ_LUT_BYTES_MAX &&
+            pp.s.rows_per_block < lut_floor) {
+            pp.s.rows_per_block = (lut_floor + 255) / 256 * 256;
+            while ((pp.s.N + pp.s.rows_per_block - 1) / pp.s.rows_per_block > 65535) pp.s.rows_per_block *= 2;
+        }
+        HIP_TRY(wv_launch_sbd_pq_scan(&pp, s));
+        return WV_OK;
+    }
+    // manhattan, hamming: the tiled kernel's threshold epilogue (wv_l1.hip)
+    wv::L1Params lp{};
+    l1_fill(ix, &lp);
+    lp.Q = sp.Q;
+    lp.ldq = sp.dpad;
+    lp.nq = sp.nq;
+    lp.allow = sp.allow;
+    lp.allow_nbits = sp.allow_nbits;
+    lp.allow_stride = sp.allow_stride;
+    l1_schedule_for(ix, sp.nq, &lp);
+    lp.target = sp.target;
+    lp.cap = sp.cap;
+    lp.keys = sp.keys;
+    lp.cnt = sp.cnt;
+    HIP_TRY(wv_launch_l1_thresh(&lp, s));
+    return WV_OK;
+}
 
 // rows per workgroup of the scan: ~4 blocks per CU over the scanned queries,
 // whole 4-wave steps of 256 rows
@@ -427,40 +473,8 @@ int wv_search_by_vector_distance_batch(wv_index* ix, const float* queries, int n
                 sp.nq = nq;
                 sp.rows_per_block = sbd_scan_rows(ix, sp.N, nq);
                 sp.cap = cap;
-                if (ix->pq_on) {
-                    wv::SbdPqParams pp{};
-                    pp.pq = pq_params(ix);
-                    pp.lut = sbd_pq_lut();
-                    // A workgroup that builds the table reads ks * D centroid
-                    // floats, 4 ks ds bytes a segment, against the m code bytes of
-                    // each row: from 4 ks ds rows a block the table's traffic is at
-                    // most the block's code traffic (and its ks * D multiply-adds
-                    // at most a quarter of its rows' m gathers), so that is the
-                    // floor where it exceeds 4096 (ks 256, ds 4: the same 4096).
-                    const uint64_t lut_floor = 4 * (uint64_t)pp.pq.ks * (uint64_t)pp.pq.ds;
-                    if (pp.lut != 0 && (uint64_t)pp.pq.m * pp.pq.ks * 4 <= (uint64_t)wv::SBD_PQ_LUT_BYTES_MAX &&
-                        sp.rows_per_block < lut_floor) {
-                        sp.rows_per_block = (lut_floor + 255) / 256 * 256;
-                        while ((sp.N + sp.rows_per_block - 1) / sp.rows_per_block > 65535) sp.rows_per_block *= 2;
-                    }
-                    pp.s = sp;
-                    HIP_TRY(wv_launch_sbd_pq_scan(&pp, s));
-                } else if (metric_is_l1(ix->metric)) {
-                    // manhattan, hamming: the tiled kernel's threshold epilogue (wv_l1.hip)
-                    wv::L1Params lp{};
-                    l1_fill(ix, &lp);
-                    lp.Q = sp.Q;
-                    lp.ldq = sp.dpad;
-                    lp.nq = nq;
-                    lp.allow = sp.allow;
-                    lp.allow_nbits = sp.allow_nbits;
-                    lp.allow_stride = sp.allow_stride;
-                    l1_schedule_for(ix, nq, &lp);
-                    lp.target = sp.target;
-                    lp.cap = cap;
-                    lp.keys = sp.keys;
-                    lp.cnt = sp.cnt;
-                    HIP_TRY(wv_launch_l1_thresh(&lp, s));
+                if (sbd_kind_has_pass(ix)) {
+                    if (int rc = sbd_kind_pass(ix, sp, s)) return rc;
                 } else if (sbd_h16_ok(ix)) {
                     ccap = sbd_h16_cand(cap);
                     scan_p = sp;

@@ -56,7 +56,10 @@ hipError_t wv_launch_sbd_h16_count(const uint64_t* excl, const uint64_t* allow, 
 hipError_t wv_launch_sbd_h16(const wv::SbdH16Params* p, hipStream_t s);
 hipError_t wv_launch_sbd_h16w(const wv::SbdH16WParams* p, hipStream_t s);
 hipError_t wv_launch_bigk_bound(const wv::BigkParams* p, hipStream_t s);
+hipError_t wv_launch_bigk_tau(const wv::BigkParams* p, hipStream_t s);
 hipError_t wv_launch_bigk_emit(const wv::BigkParams* p, hipStream_t s);
+hipError_t wv_launch_bigk_bound_pq(const wv::BigkPqParams* p, hipStream_t s);
+hipError_t wv_launch_bigk_bound_l1(const wv::BigkParams* p, hipStream_t s);
 hipError_t wv_launch_sbd_pq_scan(const wv::SbdPqParams* p, hipStream_t s);
 hipError_t wv_launch_sbd_pq_ids(const wv::SbdPqIdsParams* p, hipStream_t s);
 hipError_t wv_launch_pq_encode(const float* X, int ldx, const uint64_t* ids, uint64_t n_rows, const wv::PqParams* pq,

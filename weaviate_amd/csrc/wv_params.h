@@ -557,6 +557,14 @@ constexpr int BIGK_SEG_MIN = 1024;         // sampled rows per workgroup, at lea
 constexpr int BIGK_ONE_QUERY_KMAX = 600;
 constexpr int BIGK_FEW_NQ = 3;
 constexpr int BIGK_FEW_QUERIES_KMAX = 2000;
+// The other index kinds (profiles/large_k_kinds/README.md, 1M x 128): manhattan
+// keeps these cut-offs (one query at k = 600: 0.30 against 0.31 ms).  A single
+// hamming query never gains -- the tiled kernel's threshold pass alone is 0.21
+// ms of the scan and sort's 0.31, 0.36 in all at k = 600 -- so it stays on the
+// per-query route at every k.  A compressed index has no cut-off: its
+// per-query route sorts every row's key, 22.6 ms a query, against 0.28 to
+// 0.78 ms on the route for one query at k = 600 to 4096.
+constexpr int BIGK_ONE_QUERY_KMAX_HAMMING = 0;
 struct BigkParams {
     const float* X;
     const float* Q;           // [nq][dpad] (normalized if cosine)
@@ -722,6 +730,15 @@ struct SbdPqParams {
 };
 struct SbdPqIdsParams {
     SbdIdsParams s;
+    PqParams pq;
+    int lut;
+    uint64_t lut_min_rows;
+};
+// The large-k route's bound pass on a compressed index (wv_bigk_kinds.hip):
+// BigkParams' sample and selection, the distance from the codes as above; a
+// workgroup's share is its segment's samples.  X, D and ldx are not read.
+struct BigkPqParams {
+    BigkParams b;
     PqParams pq;
     int lut;
     uint64_t lut_min_rows;

@@ -90,6 +90,12 @@ uint64_t sbd_scan_rows(const wv_index* ix, uint64_t N, int nqs);
 bool sbd_h16_ok(const wv_index* ix);
 int sbd_h16_cand(int cap);
 int sbd_h16_pass(wv_index* ix, const wv::SbdParams& sp, int ccap, hipStream_t s);
+// ... and the threshold pass of a compressed, manhattan or hamming index over
+// the same staged batch; WV_SBD_PQ_LUT (-1 unset), which the compressed passes
+// and the route's bound pass over codes read alike
+bool sbd_kind_has_pass(const wv_index* ix);
+int sbd_kind_pass(wv_index* ix, const wv::SbdParams& sp, hipStream_t s);
+int sbd_pq_lut();
 
 // wv_search_hnsw.hip: the graph search, beside an exact pass over the delta set
 int choose_vc_log2(int per_wave_budget_words, int fixed_words, uint64_t n_nodes, int* tbits);

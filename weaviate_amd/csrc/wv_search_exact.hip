@@ -757,8 +757,13 @@ int queue_fbd(wv_index* ix, const Batch& b) {
 // contains every row any query may return (the delta set of wv_index_add);
 // its rows are compacted and each query's own list is tested per row.
 int run_exact(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_t rowmask_nbits) {
-    if (ix->pq_on)   // flatSearch on a compressed index ranks by PQ distance (index.go:493-511)
+    if (ix->pq_on) {   // flatSearch on a compressed index ranks by PQ distance (index.go:493-511)
+        // k past the fused scan (without it: past BF_FAST_KMAX) on the batched
+        // large-k route where the index asks for it, not the nq x N sort
+        const bool fused = ix->pq_scan && b.k <= 256 && wv::pq_ok(pq_params(ix));
+        if (!fused && b.k > wv::BF_FAST_KMAX && ix->n_rows && b.nq && bigk_ok(ix, b)) return run_bigk(ix, b);
         return run_pq_flat(ix, b, d_rowmask, rowmask_nbits);
+    }
     const uint64_t N = ix->n_rows;
     const float* d_q = b.q;
     const int nq = b.nq, k = b.k;
@@ -766,8 +771,12 @@ int run_exact(wv_index* ix, const Batch& b, const uint64_t* d_rowmask, uint64_t 
     const uint64_t allow_nbits = b.allow_nbits, allow_stride = b.allow_stride;
     hipStream_t s = b.s;
     if (N == 0 || nq == 0) return no_rows(b);
-    // manhattan, hamming: one kernel whatever the filter; larger k by scan and sort
-    if (metric_is_l1(ix->metric)) return k <= wv::L1_KMAX ? run_l1(ix, b) : exact_each(ix, b, nullptr);
+    // manhattan, hamming: one kernel whatever the filter; larger k on the
+    // large-k route where the index asks for it, else by scan and sort
+    if (metric_is_l1(ix->metric)) {
+        if (k <= wv::L1_KMAX) return run_l1(ix, b);
+        return bigk_ok(ix, b) ? run_bigk(ix, b) : exact_each(ix, b, nullptr);
+    }
     // the f16 pass (whole corpus or a shared allow list) serves k up to
     // BF_WIDE_KMAX; the other key passes k up to BF_FAST_KMAX
     const bool h16_ok = ix->use_h16 && !allow_stride && !d_rowmask;

@@ -332,8 +332,10 @@ class GPUVectorIndex:
 
     def set_large_k(self, on: bool = True):
         """Flat k-NN past every key pass (k > 256, or k > 32 with per-query
-        bitmaps; k <= 4096) by the batched large-k route (on) or a scan and
-        sort per query (off, the default).  Same answers."""
+        bitmaps; k > 128 on a manhattan or hamming index; on a compressed one
+        every k > 32 the fused scan does not serve; k <= 4096) by the batched
+        large-k route (on) or a scan and sort per query (off, the default).
+        Same answers."""
         check(lib().wv_index_set_large_k(self._h, int(on)))
 
     def last_large_k_stats(self):
